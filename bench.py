@@ -25,10 +25,12 @@ every step — local reduce AND cross-rank combine — completes before the next
 captured hipGraphs (``--launch``; captured after eager warm-up steps and replayed once untimed:
 eager Python issue leaves ~22 us GPU gaps per step). The headline phase runs under a deadline
 (``--headline-deadline``): past it rank 0 prints a diagnostic JSON line and every rank exits
-non-zero instead of waiting out the process-group timeout. Only after the line is final do the
-extras run (pipelined / 2-lane / RCCL candidates, reduce.c's element-wise table, the xGMI peer-read
-probe), under their own watchdog (``--extras-deadline``): a hung extra still leaves the printed,
-verified headline; the teardown after the line (``--teardown-deadline``) is bounded the same way.
+non-zero instead of waiting out the process-group timeout. A plain run stops there: set-up, warm-up,
+the K timed steps, their verification, the line (and ``--dump-outputs DIR``: the last timed step's
+result as ``DIR/result.npy``). With ``--full``, after the line is final the extras run (the
+decomposition, pipelined / 2-lane / RCCL candidates, reduce.c's element-wise table, the xGMI
+peer-read probe), under their own watchdog (``--extras-deadline``): a hung extra still leaves the
+printed, verified headline; the teardown after the line (``--teardown-deadline``) is bounded the same way.
 Every step's result is checked after timing against torch's own fp64 reduction
 of the shards (AND over ranks), and every device-side error word (polled fan-in, fused finish) is
 read and agreed over ranks.
@@ -225,8 +227,16 @@ def parse_args(argv=None):
     p.add_argument("--gpus", type=int, default=None,
                    help="GPUs (ranks) of the job; default: WORLD_SIZE under a launcher, else 1. Without a "
                         "launcher, N > 1 starts N ranks (a child torch.distributed.run)")
-    p.add_argument("--steps", type=int, default=50)
+    p.add_argument("--steps", type=int, default=50, help="timed steps (exactly this many are timed)")
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run the extras (decomposition, pipelined / RCCL candidates, "
+                        "reduce.c's element-wise table, the xGMI peer-read probe, --compare-torch); a plain run "
+                        "measures and verifies the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps rank 0 writes what the last timed step computed to DIR/<name>.npy "
+                        "(float64; a fixed seeded sample of an output above 32 MB). The inputs are the same in "
+                        "every run with the same arguments, so two builds can be compared output for output")
     p.add_argument("--config", default=NORTH_STAR, choices=sorted(CONFIGS))
     p.add_argument("--elements", type=int, default=None, help="override the global element count")
     p.add_argument("--pipelined", action="store_true",
@@ -237,7 +247,7 @@ def parse_args(argv=None):
                    help="seconds the headline phase (setup, self-check, plan tuning, timed steps, verification) "
                         "may take; past it rank 0 prints a diagnostic JSON line and every rank exits with 2")
     p.add_argument("--no-candidates", dest="candidates", action="store_false",
-                   help="skip the after-headline candidate measurements (pipelined 2-lane fused finish, RCCL "
+                   help="--full: skip the after-headline candidate measurements (pipelined 2-lane fused finish, RCCL "
                         "serial / pipelined)")
     p.add_argument("--collective", choices=["auto", "rccl", "fused"], default="auto",
                    help="cross-rank combine: rccl = 1-element RCCL all-reduce after the local kernel; "
@@ -265,17 +275,17 @@ def parse_args(argv=None):
                    help="vector (reduce.c) configs: torch.distributed collective, or the one-kernel direct "
                         "peer-read collective over xGMI (GPUs)")
     p.add_argument("--no-vector-extras", dest="vector_extras", action="store_false",
-                   help="north-star runs also time reduce.c's element-wise table (INT / DOUBLE x MAX / MIN / SUM of "
+                   help="north-star --full runs also time reduce.c's element-wise table (INT / DOUBLE x MAX / MIN / SUM of "
                         "2 GiB to root 0, plus DOUBLE SUM all-reduce; RCCL and direct) and report it as "
                         "reduce_c_vector; this skips that")
     p.add_argument("--extras-deadline", type=float, default=240.0,
-                   help="seconds the reduce.c extras may take after the headline; past it rank 0 prints the "
+                   help="--full: seconds the extras may take after the headline; past it rank 0 prints the "
                         "headline (extras marked as timed out) and the run ends")
     p.add_argument("--teardown-deadline", type=float, default=120.0,
                    help="seconds the teardown after the printed line (device sync, process-group destruction) "
                         "may take; past it every rank exits with the headline's status")
     p.add_argument("--no-decompose", dest="decompose", action="store_false",
-                   help="skip the after-headline decomposition (the same steps without the combine, per rank: "
+                   help="--full: skip the after-headline decomposition (the same steps without the combine, per rank: "
                         "local time, skew, exchange cost)")
     p.add_argument("--local-only", action="store_true",
                    help="single rank: skip the cross-rank combine (by default it is issued even at N=1)")
@@ -319,7 +329,7 @@ def parse_args(argv=None):
                         "next to bench.py. The printed line carries only the headline and a summary")
     p.add_argument("--no-verify", action="store_true")
     p.add_argument("--compare-torch", action="store_true",
-                   help="after the measurement, time torch's own reduction of the same shard (reported as "
+                   help="--full: after the measurement, time torch's own reduction of the same shard (reported as "
                         "torch_gbps; not part of the metric)")
     p.add_argument("--trace", action="store_true", help="roctx range per step (rocprofv3 --marker-trace)")
     p.add_argument("--backend", choices=["auto", "nccl", "gloo"], default="auto",
@@ -333,6 +343,24 @@ def parse_args(argv=None):
 def _sync(dev: torch.device) -> None:
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
+
+
+DUMP_MAX_ELEMENTS = 4 << 20  # per dumped array: 32 MB as float64
+
+
+def _dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: one ``<name>.npy`` per array in ``out_dir``, as float64 (integer and narrower
+    floating results are widened). An array above DUMP_MAX_ELEMENTS is sampled at fixed positions
+    (seeded: the same in every run), so two builds' dumps compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            g = torch.Generator(device="cpu").manual_seed(0x5EED)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMENTS,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.to(torch.float64).cpu().numpy())
 
 
 def _ranks_seen(ctx) -> int:
@@ -454,6 +482,8 @@ def run_vector(args, ctx, cfg, fault) -> int:
     wl = VectorReduction(cfg, ctx, impl=args.vector_impl).setup(mt19937=(ctx.device.type == "cpu"))
     dev = ctx.device
     elapsed, verified = _time_vector(wl, ctx, args.steps, args.warmup, fault, not args.no_verify)
+    if args.dump_outputs and ctx.is_root:  # the last timed collective's result (rank 0 holds it in both forms)
+        _dump_outputs(args.dump_outputs, {"result": wl.result()})
     gib = wl.bytes_total * args.steps / elapsed / float(1 << 30)
     seen = _ranks_seen(ctx)
     if seen != ctx.world_size:
@@ -790,10 +820,13 @@ def _measure(wl, slots, ctx, args, fault, serial: bool, warmup: int, allow_graph
     elapsed = pdist.max_over_ranks(t1 - t0, ctx)
     fastest = -pdist.max_over_ranks(-(t1 - t0), ctx)
     written = warmup + (sg.chunk if sg is not None else K)
+    # the slot the last timed step wrote (a replayed chunk rewrites the chunk's slots; the remainder
+    # graph, if any, runs last)
+    last = warmup + ((sg.rem or sg.chunk) if sg is not None else K) - 1
     if sg is not None:
         sg.reset()  # captured RCCL work must not outlive the communicator
     return {"elapsed": elapsed, "elapsed_min": fastest, "elapsed_local": t1 - t0, "launch": launch,
-            "written": written}
+            "written": written, "last": last}
 
 
 def _replay_probe(wl, ctx, args, fault, serial: bool, step, capture: bool) -> "str | None":
@@ -1638,6 +1671,8 @@ def _main(argv=None) -> int:
             verified = False
         if err is not None and ctx.is_root:
             print(f"[bench] device error: {err}", file=sys.stderr)
+        if args.dump_outputs and ctx.is_root and K > 0:  # what the last timed step returned to its caller
+            _dump_outputs(args.dump_outputs, {"result": slots[m["last"]:m["last"] + 1]})
         return m, err, seen, verified, ref
 
     m, err, seen, verified, ref = timed("timed steps")
@@ -1760,17 +1795,20 @@ def _main(argv=None) -> int:
     # longer fit in the run budget are skipped (agreed over ranks).
     room = _budget_left(args) - EXTRAS_RESERVE_S  # what the run budget leaves for the extras
     extras_deadline = max(0.01, min(args.extras_deadline, room))
-    do_extras = -pdist.max_over_ranks(-float(room >= EXTRAS_MIN_S), ctx) > 0.5  # AND over ranks
+    # (a plain run has none: they run with --full only)
+    do_extras = args.full and -pdist.max_over_ranks(-float(room >= EXTRAS_MIN_S), ctx) > 0.5  # AND over ranks
     extras = record.extras if record is not None else {}
     # (skipped extras run nothing: their guard only covers writing the record)
     guard = _ExtrasWatchdog(record, extras_deadline if do_extras else 10.0, rc)
 
     def rearm() -> None:  # the finished headline + the extras so far, should the process be killed now
-        if record is not None:
+        if record is not None and not args.full:
+            _arm(record.final(error="the process was terminated (signal) after the headline was measured"))
+        elif record is not None:
             _arm(record.final(error="the process was terminated (signal) during the extras; headline measured "
                                     "and verified before them"))
     rearm()
-    if not do_extras:
+    if args.full and not do_extras:
         extras["skipped"] = f"run budget: {max(0.0, _budget_left(args)):.0f} s left after the headline"
     run_cands = do_extras and args.candidates and dev.type == "cuda" and hasattr(wl, "use_collective") \
         and not args.pipelined

@@ -138,10 +138,39 @@ def test_bench_contract_on_cpu_ranks(tmp_path):
     assert abs(d["value"] - d["config"]["bytes_per_step"] * 4 / (d["ms_per_step"] * 4e-3) / 1e9) / d["value"] < 0.01
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_result(tmp_path):
+    # a plain run sets up, warms up, times exactly --steps steps, verifies them and prints the line:
+    # the extras need --full. --dump-outputs writes what the last timed step returned, and the inputs
+    # are the same in every run with the same arguments.
+    import numpy as np
+    from cuda_mpi_reductions_amd.ops import synthetic
+    got = []
+    for k in range(2):
+        dump = tmp_path / f"dump{k}"
+        r = run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                 "--device", "cpu", "--elements", "200003", "--dump-outputs", str(dump)], cwd=tmp_path, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = bench_record(r.stdout)
+        assert d["verified"] is True and d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert d["dtype"] == "fp64" and d["unit"] == "GB/s" and d["higher_is_better"] is True
+        for key in ("decomposition", "candidates", "reduce_c_vector", "torch_gbps"):
+            assert key not in d, key
+        assert "extras_skipped" not in d["summary"] and "extras_error" not in d["summary"]
+        assert sorted(p.name for p in dump.iterdir()) == ["result.npy"]
+        a = np.load(dump / "result.npy")
+        assert a.dtype == np.float64 and a.shape == (1,)
+        got.append(float(a[0]))
+    ref = synthetic(200003, torch.float64, seed=0x5EED).sum().item()
+    # any summation order of n non-negative fp64 terms is within n * eps of the exact sum, relatively
+    tol = 200003 * 2.0 ** -52 * ref
+    assert abs(got[0] - ref) <= tol and abs(got[1] - ref) <= tol, (got, ref)
+    assert abs(got[0] - got[1]) <= tol
+
+
 def test_bench_self_launches_n_ranks_without_torchrun(tmp_path):
     # `python bench.py --gpus 2` with no launcher starts 2 ranks itself (a child
     # torch.distributed.run; the parent never touches a GPU) and proves the shape in the JSON
-    r = run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu", "--steps", "3",
+    r = run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--device", "cpu", "--steps", "3",
              "--warmup", "1", "--elements", "200003"], cwd=tmp_path, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -162,7 +191,7 @@ def test_bench_self_launches_n_ranks_without_torchrun(tmp_path):
 def test_bench_four_cpu_ranks_probe_and_decomposition(tmp_path):
     # the N > 1 headline flow with 4 ranks: the replay probe runs (auto: the combine issues a
     # collective at N > 1; eager here) and passes, the decomposition covers every rank
-    r = torchrun(4, [os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "5", "--warmup", "1",
+    r = torchrun(4, [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--steps", "5", "--warmup", "1",
                      "--device", "cpu", "--elements", "400007"], cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     d = bench_record(r.stdout)
@@ -181,7 +210,7 @@ def test_bench_line_is_compact_and_self_proving_at_eight_ranks(tmp_path):
     # only the contract keys, the proof fields (verified, ranks_seen, rccl_ranks_seen among the first,
     # launcher, native source hash) and a small summary; the full extras go to the sidecar it names.
     side = tmp_path / "extras8.json"
-    r = torchrun(8, [os.path.join(ROOT, "bench.py"), "--gpus", "8", "--device", "cpu", "--steps", "3",
+    r = torchrun(8, [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--device", "cpu", "--steps", "3",
                      "--warmup", "1", "--elements", "800009", "--extras-file", str(side)], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -213,7 +242,7 @@ def test_bench_refuses_world_size_mismatch(tmp_path):
 
 
 def test_bench_external_launcher_recorded(tmp_path):
-    r = torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = torchrun(2, [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                      "--device", "cpu", "--elements", "100003", "--no-decompose"], cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     d = bench_record(r.stdout)
@@ -351,7 +380,7 @@ def test_bench_budget_too_small_for_extras_skips_them(tmp_path):
     # injected 8 s straggler) leaves less than the extras' minimum window, the extras are skipped on
     # every rank (agreed) and the line says so
     side = tmp_path / "x.json"
-    r = torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu", "--steps", "3", "--warmup", "1",
+    r = torchrun(2, [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--device", "cpu", "--steps", "3", "--warmup", "1",
                      "--elements", "200003", "--budget", "45", "--inject-fault", "delay=8000@0:1",
                      "--extras-file", str(side)], cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -166,7 +166,7 @@ def test_crashed_rank_fails_job_fast(tmp_path):
 def test_rank_killed_during_extras_keeps_the_verified_headline(tmp_path):
     # the headline is final, then rank 1 dies in the first extra: torchrun SIGTERMs rank 0, whose
     # signal handler prints the armed line — the measured, verified headline — exactly once
-    r = torchrun(2, [BENCH, *SCALAR, "--inject-fault", "exit@1:0/extras"], cwd=tmp_path, timeout=300)
+    r = torchrun(2, [BENCH, "--full", *SCALAR, "--inject-fault", "exit@1:0/extras"], cwd=tmp_path, timeout=300)
     assert r.returncode != 0  # the job did fail
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

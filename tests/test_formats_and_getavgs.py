@@ -1,13 +1,13 @@
 """Output-format parity with the reference and the getAvgs.sh re-implementation,
-checked against the reference's own shipped data (read-only text files)."""
+checked against the reference's own recorded results (tests/golden/reference_mpi: its raw outputs,
+collected.txt and results/, text files)."""
 import os
 
 import pytest
 
 from cuda_mpi_reductions_amd.utils import formats, getavgs
 
-REF = "/root/reference/mpi"
-have_ref = os.path.isdir(REF)
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_mpi")
 
 
 def test_gnuplot_line_matches_reduce_c_printf():
@@ -24,7 +24,6 @@ def test_throughput_line_matches_reduction_cpp():
     assert formats.parse_throughput(line)["elements"] == 16777216
 
 
-@pytest.mark.skipif(not have_ref, reason="reference data not mounted")
 def test_parse_reference_raw_outputs():
     rows = []
     for name in sorted(os.listdir(os.path.join(REF, "raw_output"))):
@@ -35,7 +34,6 @@ def test_parse_reference_raw_outputs():
     assert {r.op for r in rows} == {"MAX", "MIN", "SUM"}
 
 
-@pytest.mark.skipif(not have_ref, reason="reference data not mounted")
 def test_getavgs_reproduces_reference_results(tmp_path):
     getavgs.write_results(os.path.join(REF, "collected.txt"), str(tmp_path))
     for dt in ("INT", "DOUBLE"):
@@ -65,7 +63,6 @@ def test_python_cli_grammar():
         cli.parse(["method=SUM"])
 
 
-@pytest.mark.skipif(not have_ref, reason="reference data not mounted")
 def test_getavgs_averages_the_co_mode_raw_outputs():
     """The BG/L CO-mode runs were never averaged by the reference's authors:
     getAvgs over the concatenated `stdout-co-*` files gives the table the survey quotes."""

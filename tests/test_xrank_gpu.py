@@ -65,7 +65,7 @@ def test_fused_world1_matches_torch(dt, op, n):
 def test_bench_torchrun_one_rank_graphs_both_modes(tmp_path, collective):
     # the cross-rank combine is issued at world 1 and captured into graphs for both
     # the pipelined headline and the serial measurement.
-    r = torchrun(1, [BENCH, "--no-vector-extras", "--gpus", "1", "--steps", "8", "--warmup", "2", "--elements", "50000017",
+    r = torchrun(1, [BENCH, "--full", "--no-vector-extras", "--gpus", "1", "--steps", "8", "--warmup", "2", "--elements", "50000017",
                      "--collective", collective], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json(r)
@@ -211,7 +211,7 @@ def test_bench_auto_falls_back_to_rccl_on_every_rank(tmp_path, monkeypatch):
 def test_bench_auto_headline_is_serial_fused_extras_after(tmp_path):
     # value = the serial one-lane fused measurement; the pipelined 2-lane number is
     # an extra measured after the line is final; at world 1 there is no RCCL combine to measure.
-    r = run([sys.executable, BENCH, "--no-vector-extras", "--steps", "12", "--warmup", "2", "--elements", "50000017"],
+    r = run([sys.executable, BENCH, "--full", "--no-vector-extras", "--steps", "12", "--warmup", "2", "--elements", "50000017"],
             cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json(r)
@@ -275,7 +275,7 @@ def test_bench_vector_direct_ranks_share_one_gpu(tmp_path, nproc, monkeypatch):
 
 
 def test_bench_vector_extras_in_headline(tmp_path):
-    r = run([sys.executable, BENCH, "--steps", "4", "--warmup", "1", "--elements", "50000017", "--no-candidates"],
+    r = run([sys.executable, BENCH, "--full", "--steps", "4", "--warmup", "1", "--elements", "50000017", "--no-candidates"],
             cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json(r)
@@ -335,7 +335,7 @@ def test_bench_auto_remeasures_over_rccl_when_fused_fails_the_headline(tmp_path,
 
 def test_bench_eight_ranks_fused_on_one_gpu(tmp_path, monkeypatch):
     monkeypatch.setenv("MIREDUCE_FORCE_DEVICE", "0")
-    r = torchrun(8, [BENCH, "--gpus", "8", "--backend", "gloo", "--collective", "fused", "--steps", "12",
+    r = torchrun(8, [BENCH, "--full", "--gpus", "8", "--backend", "gloo", "--collective", "fused", "--steps", "12",
                      "--warmup", "2", "--elements", "40000003", "--graph-chunk", "6", "--no-vector-extras"],
                  cwd=tmp_path, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -349,7 +349,7 @@ def test_bench_eight_ranks_fused_on_one_gpu(tmp_path, monkeypatch):
 def test_bench_eight_ranks_auto_on_one_gpu(tmp_path, monkeypatch):
     # the driver's default command at N=8 (auto-tuned combine), rehearsed with gloo on one GPU
     monkeypatch.setenv("MIREDUCE_FORCE_DEVICE", "0")
-    r = torchrun(8, [BENCH, "--gpus", "8", "--backend", "gloo", "--steps", "12", "--warmup", "2",
+    r = torchrun(8, [BENCH, "--full", "--gpus", "8", "--backend", "gloo", "--steps", "12", "--warmup", "2",
                      "--elements", "40000003", "--tune-steps", "4"], cwd=tmp_path, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json(r)
@@ -385,7 +385,7 @@ def test_reduce_xgmi_direct_eight_ranks_on_one_gpu():
 def test_bench_extras_deadline_keeps_the_headline(tmp_path):
     # reduce.c extras past their deadline: the headline line is still printed (extras marked as
     # timed out) and the run ends with the headline's status.
-    r = run([sys.executable, BENCH, "--steps", "4", "--warmup", "1", "--elements", "50000017",
+    r = run([sys.executable, BENCH, "--full", "--steps", "4", "--warmup", "1", "--elements", "50000017",
              "--extras-deadline", "0.05"], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -401,7 +401,7 @@ def test_bench_extras_hang_in_rccl_candidate_keeps_the_headline(tmp_path, monkey
     # a hang inside an after-headline RCCL candidate (fault site "extras") still
     # ends the run with the verified headline printed and rc 0 (the extras watchdog), on every rank.
     monkeypatch.setenv("MIREDUCE_FORCE_DEVICE", "0")
-    r = torchrun(2, [BENCH, "--no-vector-extras", "--gpus", "2", "--backend", "gloo", "--collective", "rccl",
+    r = torchrun(2, [BENCH, "--full", "--no-vector-extras", "--gpus", "2", "--backend", "gloo", "--collective", "rccl",
                      "--steps", "4", "--warmup", "1", "--elements", "20000003", "--extras-deadline", "25",
                      "--inject-fault", "hang@1:0/extras"], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -450,7 +450,7 @@ def test_bench_replay_probe_and_decomposition_one_gpu(tmp_path):
     # VERDICT r3 items 2 and 4 on the GPU path: the RCCL combine captured at world 1 runs the replay
     # probe (forced on) and passes it; the decomposition's local time is the same kernel without
     # the combine, so at world 1 the exchange costs little.
-    r = run([sys.executable, BENCH, "--no-vector-extras", "--no-candidates", "--steps", "40", "--warmup", "2",
+    r = run([sys.executable, BENCH, "--full", "--no-vector-extras", "--no-candidates", "--steps", "40", "--warmup", "2",
              "--elements", "50000017", "--collective", "rccl", "--replay-probe", "on"], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json(r)

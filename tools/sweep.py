@@ -9,7 +9,7 @@ reduce.c-format line into ``<out>/collected.txt``, averages them (tools/getAvgs.
 ``<out>/results/`` and, for bench.py, collects the JSON lines into ``<out>/bench.jsonl``.
 
     python tools/sweep.py --app reduce_xgmi --ranks 1,2,4,8 --out runs/vector -- --mode=vector
-    python tools/sweep.py --app bench --ranks 1,2,4,8 --out runs/bench -- --steps 50 --warmup 10
+    python tools/sweep.py --app bench --ranks 1,2,4,8 --out runs/bench -- --full --steps 50 --warmup 10
     python tools/sweep.py --app reduce_mpi --ranks 2,4 --out runs/mpi -- --ints=1M --doubles=1M
     python tools/sweep.py --preset node --out runs/node      # the whole 1/2/4/8-GPU matrix below
 
@@ -85,7 +85,7 @@ def node_preset(extra: list[str]) -> list[tuple]:
     for coll in ("allreduce", "fused"):  # simpleMPI's scalar combine: RCCL vs the in-kernel fused finish
         entries.append(("reduce_xgmi", f"scalar-{coll}", "ranks",
                         ["--mode=scalar", f"--collective={coll}", "--graph", "--dtypes=INT,DOUBLE"] + extra))
-    entries.append(("bench", "bench", "ranks", ["--steps", "50", "--warmup", "10"]))
+    entries.append(("bench", "bench", "ranks", ["--full", "--steps", "50", "--warmup", "10"]))
     return entries
 
 
