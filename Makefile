@@ -166,7 +166,7 @@ $(BUILD)/bin/cpp_consumer: examples/cpp_consumer/main.cpp $(SHLIB) $(HEADERS)
 	$(HOSTCXX) $(HOSTFLAGS) $< $(LINK_BIN) $(LDLIBS) -o $@
 
 # Native unit tests (host code only) and the bootstrap multi-process test.
-UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/bootstrap_test
+UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/bootstrap_test
 unit: $(UNIT)
 
 UNIT_SRCS := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
@@ -174,6 +174,13 @@ $(BUILD)/bin/host_unit: tests/native/host_unit.cpp $(UNIT_SRCS) $(HEADERS)
 	@mkdir -p $(dir $@)
 	g++ $(CXXSTD) -O2 -Wall -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP tests/native/host_unit.cpp \
 	    $(UNIT_SRCS) -o $@
+
+# cpu_scan against a naive loop (tests/native/scan_unit.cpp; host code only, as race_unit).
+SCAN_UNIT_SRCS := tests/native/scan_unit.cpp csrc/runtime/scan_cpu.cpp
+SCAN_UNIT_FLAGS := -Icsrc/include -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -DMIREDUCE_NO_HIP
+$(BUILD)/bin/scan_unit: $(SCAN_UNIT_SRCS) $(HEADERS)
+	@mkdir -p $(dir $@)
+	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SCAN_UNIT_SRCS) -o $@
 
 $(BUILD)/bin/bootstrap_test: tests/native/bootstrap_test.cpp $(COMMLIB) $(SHLIB) $(HEADERS)
 	@mkdir -p $(dir $@)
@@ -188,6 +195,8 @@ asan: csrc/apps/reduce_mpi.cpp
 	    -o $(BUILD)/asan/reduce_mpi
 	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP \
 	    tests/native/host_unit.cpp $(UNIT_SRCS) -o $(BUILD)/asan/host_unit
+	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
+	    $(SCAN_UNIT_SRCS) -o $(BUILD)/asan/scan_unit
 
 # Race detection: the threaded host reference reducers / arg-reductions under
 # ThreadSanitizer (tests/native/race_unit.cpp; exits non-zero on any report).

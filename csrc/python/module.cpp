@@ -23,6 +23,7 @@
 #include "mireduce/reduce.hpp"
 #include "mireduce/reduce_dim.hpp"
 #include "mireduce/reduce_many.hpp"
+#include "mireduce/scan.hpp"
 #include "mireduce/trace.hpp"
 #include "mireduce/types.hpp"
 #include "mireduce/version.hpp"
@@ -543,6 +544,87 @@ PYBIND11_MODULE(_C, m) {
       py::arg("in_ptr"), py::arg("rows"), py::arg("cols"), py::arg("dtype"), py::arg("op"), py::arg("out_value_ptr"),
       py::arg("out_index_ptr"));
 
+  // Prefix scans (csrc/kernels/scan.hip, csrc/runtime/scan_cpu.cpp).
+  auto scan_cfg = [](bool single_pass, int64_t max_tiles_per_launch, int wg_per_cu, int max_blocks,
+                     uint64_t wait_bound_ticks, int64_t debug_delay_tile, uint64_t debug_delay_ticks,
+                     bool debug_delay_before_aggregate, int debug_lookback_width) {
+    ScanConfig c;
+    c.single_pass = single_pass;
+    c.max_tiles_per_launch = max_tiles_per_launch;
+    c.wg_per_cu = wg_per_cu;
+    c.max_blocks = max_blocks;
+    c.wait_bound_ticks = wait_bound_ticks;
+    c.debug_delay_tile = debug_delay_tile;
+    c.debug_delay_ticks = debug_delay_ticks;
+    c.debug_delay_before_aggregate = debug_delay_before_aggregate;
+    c.debug_lookback_width = debug_lookback_width;
+    return c;
+  };
+  auto scan_plan_dict = [](const ScanPlan& p) {
+    py::dict d;
+    d["block"] = p.block;
+    d["items_per_thread"] = p.items_per_thread;
+    d["tile_elems"] = p.tile_elems;
+    d["tiles"] = p.tiles;
+    d["grid"] = p.grid;
+    d["launches"] = p.launches;
+    d["single_pass"] = p.single_pass;
+    d["head"] = p.head;
+    d["tail"] = p.tail;
+    d["vector_stores"] = p.vector_stores;
+    return d;
+  };
+  py::class_<ScanWorkspace, std::shared_ptr<ScanWorkspace>>(m, "ScanWorkspace")
+      .def(py::init<int, int64_t>(), py::arg("device") = -1, py::arg("max_tiles") = kScanMaxTiles)
+      .def_property_readonly("device", &ScanWorkspace::device)
+      .def_property_readonly("num_cus", &ScanWorkspace::num_cus)
+      .def_property_readonly("max_tiles", &ScanWorkspace::max_tiles)
+      .def("reset", [](ScanWorkspace& w, uintptr_t stream) { w.reset(as_stream(stream)); }, py::arg("stream") = 0)
+      .def("error", &ScanWorkspace::error);
+  m.def(
+      "scan",
+      [scan_cfg, scan_plan_dict](ScanWorkspace& ws, uintptr_t in, uint64_t n, int dtype, int op, int acc, int out_dtype,
+                                 uintptr_t out, bool exclusive, uintptr_t carry_in, uintptr_t carry_out, uintptr_t stream,
+                                 bool single_pass, int64_t max_tiles_per_launch, int wg_per_cu, int max_blocks,
+                                 uint64_t wait_bound_ticks, int64_t debug_delay_tile, uint64_t debug_delay_ticks,
+                                 bool debug_delay_before_aggregate, int debug_lookback_width) {
+        const ScanConfig cfg = scan_cfg(single_pass, max_tiles_per_launch, wg_per_cu, max_blocks, wait_bound_ticks,
+                                        debug_delay_tile, debug_delay_ticks, debug_delay_before_aggregate,
+                                        debug_lookback_width);
+        return scan_plan_dict(scan(as_ptr<const void>(in), n, static_cast<DType>(dtype), static_cast<Op>(op),
+                                   static_cast<DType>(acc), static_cast<DType>(out_dtype), as_ptr<void>(out), exclusive,
+                                   as_ptr<const void>(carry_in), as_ptr<void>(carry_out), ws, as_stream(stream), cfg));
+      },
+      py::arg("ws"), py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"),
+      py::arg("out_dtype"), py::arg("out_ptr"), py::arg("exclusive") = false, py::arg("carry_in_ptr") = 0,
+      py::arg("carry_out_ptr") = 0, py::arg("stream") = 0, py::arg("single_pass") = false,
+      py::arg("max_tiles_per_launch") = 0, py::arg("wg_per_cu") = 0, py::arg("max_blocks") = 0,
+      py::arg("wait_bound_ticks") = 0, py::arg("debug_delay_tile") = -1, py::arg("debug_delay_ticks") = 0,
+      py::arg("debug_delay_before_aggregate") = false, py::arg("debug_lookback_width") = 0);
+  m.def(
+      "scan_plan",
+      [scan_cfg, scan_plan_dict](uintptr_t in, uintptr_t out, uint64_t n, int dtype, int out_dtype, int num_cus,
+                                 bool single_pass, int64_t max_tiles_per_launch, int wg_per_cu, int max_blocks) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && out_dtype >= 0 && out_dtype < kNumDTypes,
+                         "dtype out of range");
+        const ScanConfig cfg = scan_cfg(single_pass, max_tiles_per_launch, wg_per_cu, max_blocks, 0, -1, 0, false, 0);
+        return scan_plan_dict(plan_scan(as_ptr<const void>(in), as_ptr<const void>(out), n, static_cast<DType>(dtype),
+                                        static_cast<DType>(out_dtype), cfg, num_cus));
+      },
+      py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("dtype"), py::arg("out_dtype"),
+      py::arg("num_cus") = 256, py::arg("single_pass") = false, py::arg("max_tiles_per_launch") = 0,
+      py::arg("wg_per_cu") = 0, py::arg("max_blocks") = 0);
+  m.def(
+      "cpu_scan",
+      [](uintptr_t in, uint64_t n, int dtype, int op, int acc, int out_dtype, uintptr_t out, bool exclusive,
+         uintptr_t carry_in, uintptr_t carry_out) {
+        py::gil_scoped_release nogil;
+        cpu_scan(as_ptr<const void>(in), n, static_cast<DType>(dtype), static_cast<Op>(op), static_cast<DType>(acc),
+                 static_cast<DType>(out_dtype), as_ptr<void>(out), exclusive, as_ptr<const void>(carry_in),
+                 as_ptr<void>(carry_out));
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"), py::arg("out_dtype"),
+      py::arg("out_ptr"), py::arg("exclusive") = false, py::arg("carry_in_ptr") = 0, py::arg("carry_out_ptr") = 0);
   m.def(
       "moments",
       [](uintptr_t in, uint64_t n, int dtype, uintptr_t out5, uintptr_t partials, int max_grid, int num_cus,

@@ -1,0 +1,109 @@
+// Host reference of the prefix scans; see scan.hpp. Sequential: one running value in the
+// accumulator type (fp64-compensated for floating sums, rounded to the accumulator per element).
+#include <cmath>
+#include <type_traits>
+
+#include "mireduce/check.hpp"
+#include "mireduce/half.hpp"
+#include "mireduce/ops.hpp"
+#include "mireduce/scan.hpp"
+
+namespace mireduce {
+
+namespace {
+
+template <class OutT, class A>
+OutT to_out(A v) {
+  if constexpr (std::is_same_v<OutT, A>) return v;
+  else if constexpr (is_half16_v<OutT>) return OutT::from_float(v);
+  else if constexpr (std::is_integral_v<OutT>) return static_cast<OutT>(static_cast<std::make_unsigned_t<A>>(v));
+  else return static_cast<OutT>(v);
+}
+
+// The running value: Neumaier-compensated fp64 for floating sums (as cpu_reference.cpp), else the
+// accumulator itself combined with the functor.
+template <class OpT, class A>
+struct Running {
+  static constexpr bool kCompensated = std::is_same_v<OpT, SumOp> && std::is_floating_point_v<A>;
+  A plain;
+  double sum = 0, c = 0;
+  explicit Running(A start) : plain(start), sum(static_cast<double>(start)) {}
+  void add(A x) {
+    if constexpr (kCompensated) {
+      const double d = static_cast<double>(x), t = sum + d;
+      if (std::fabs(sum) >= std::fabs(d)) c += (sum - t) + d;
+      else c += (d - t) + sum;
+      sum = t;
+    } else {
+      plain = OpT::apply(plain, x);
+    }
+  }
+  A value() const {
+    if constexpr (kCompensated) return static_cast<A>(sum + c);
+    else return plain;
+  }
+};
+
+template <class OpT, class T, class A, class OutT>
+void scan_typed(const T* in, size_t n, OutT* out, bool exclusive, const A* carry_in, A* carry_out) {
+  Running<OpT, A> run(carry_in ? *carry_in : OpT::template identity<A>());
+  for (size_t i = 0; i < n; ++i) {
+    const A x = static_cast<A>(in[i]);  // read before the store: out may be in
+    if (exclusive) out[i] = to_out<OutT>(run.value());
+    run.add(x);
+    if (!exclusive) out[i] = to_out<OutT>(run.value());
+  }
+  if (carry_out) *carry_out = run.value();
+}
+
+template <class OpT, class T, class A>
+void scan_out(DType t, DType out_t, const void* in, size_t n, void* out, bool exclusive, const void* ci, void* co) {
+  const T* i = static_cast<const T*>(in);
+  const A* c0 = static_cast<const A*>(ci);
+  A* c1 = static_cast<A*>(co);
+  if constexpr (!std::is_same_v<T, A>) {
+    if (out_t == t) return scan_typed<OpT, T, A, T>(i, n, static_cast<T*>(out), exclusive, c0, c1);
+  }
+  scan_typed<OpT, T, A, A>(i, n, static_cast<A*>(out), exclusive, c0, c1);
+}
+
+template <class OpT>
+void scan_op(DType t, DType acc, DType out_t, const void* in, size_t n, void* out, bool ex, const void* ci, void* co) {
+  switch (t) {
+    case DType::Int32:
+      if (acc == DType::Int32) return scan_out<OpT, int32_t, int32_t>(t, out_t, in, n, out, ex, ci, co);
+      return scan_out<OpT, int32_t, int64_t>(t, out_t, in, n, out, ex, ci, co);
+    case DType::Int64: return scan_out<OpT, int64_t, int64_t>(t, out_t, in, n, out, ex, ci, co);
+    case DType::Float32:
+      if (acc == DType::Float32) return scan_out<OpT, float, float>(t, out_t, in, n, out, ex, ci, co);
+      return scan_out<OpT, float, double>(t, out_t, in, n, out, ex, ci, co);
+    case DType::Float64: return scan_out<OpT, double, double>(t, out_t, in, n, out, ex, ci, co);
+    case DType::BFloat16: return scan_out<OpT, bf16_t, float>(t, out_t, in, n, out, ex, ci, co);
+    case DType::Float16: return scan_out<OpT, f16_t, float>(t, out_t, in, n, out, ex, ci, co);
+  }
+}
+
+}  // namespace
+
+void cpu_scan(const void* in, size_t n, DType t, Op op, DType acc, DType out_t, void* out, bool exclusive,
+              const void* carry_in, void* carry_out) {
+  MIREDUCE_REQUIRE(op == Op::Sum || op == Op::Min || op == Op::Max, "scan: op must be SUM, MIN or MAX");
+  MIREDUCE_REQUIRE(acc_supported(t, op, acc), "scan: unsupported accumulator for this dtype / op");
+  MIREDUCE_REQUIRE(scan_out_supported(t, acc, out_t), "scan: the output type is the accumulator or the input type");
+  MIREDUCE_REQUIRE(n == 0 || (in != nullptr && out != nullptr), "scan: null pointer");
+  {
+    const char* i0 = static_cast<const char*>(in);
+    const char* o0 = static_cast<const char*>(out);
+    const size_t es = dtype_size(t), os = dtype_size(out_t);
+    const bool overlap = n && i0 < o0 + n * os && o0 < i0 + n * es;
+    MIREDUCE_REQUIRE(!overlap || (i0 == o0 && es == os),
+                     "scan: out may be in (equal element sizes) but must not overlap it otherwise");
+  }
+  switch (op) {
+    case Op::Sum: return scan_op<SumOp>(t, acc, out_t, in, n, out, exclusive, carry_in, carry_out);
+    case Op::Min: return scan_op<MinOp>(t, acc, out_t, in, n, out, exclusive, carry_in, carry_out);
+    default: return scan_op<MaxOp>(t, acc, out_t, in, n, out, exclusive, carry_in, carry_out);
+  }
+}
+
+}  // namespace mireduce
