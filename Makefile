@@ -166,7 +166,7 @@ $(BUILD)/bin/cpp_consumer: examples/cpp_consumer/main.cpp $(SHLIB) $(HEADERS)
 	$(HOSTCXX) $(HOSTFLAGS) $< $(LINK_BIN) $(LDLIBS) -o $@
 
 # Native unit tests (host code only) and the bootstrap multi-process test.
-UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/bootstrap_test
+UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/segment_unit $(BUILD)/bin/bootstrap_test
 unit: $(UNIT)
 
 UNIT_SRCS := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
@@ -181,6 +181,13 @@ SCAN_UNIT_FLAGS := -Icsrc/include -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -DMIR
 $(BUILD)/bin/scan_unit: $(SCAN_UNIT_SRCS) $(HEADERS)
 	@mkdir -p $(dir $@)
 	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SCAN_UNIT_SRCS) -o $@
+
+# cpu_segment_reduce against a naive loop, and the offset clamp / search helper of the kernels
+# (tests/native/segment_unit.cpp; host code only).
+SEGMENT_UNIT_SRCS := tests/native/segment_unit.cpp csrc/runtime/segment_cpu.cpp
+$(BUILD)/bin/segment_unit: $(SEGMENT_UNIT_SRCS) $(HEADERS)
+	@mkdir -p $(dir $@)
+	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SEGMENT_UNIT_SRCS) -o $@
 
 $(BUILD)/bin/bootstrap_test: tests/native/bootstrap_test.cpp $(COMMLIB) $(SHLIB) $(HEADERS)
 	@mkdir -p $(dir $@)
@@ -197,6 +204,8 @@ asan: csrc/apps/reduce_mpi.cpp
 	    tests/native/host_unit.cpp $(UNIT_SRCS) -o $(BUILD)/asan/host_unit
 	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
 	    $(SCAN_UNIT_SRCS) -o $(BUILD)/asan/scan_unit
+	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
+	    $(SEGMENT_UNIT_SRCS) -o $(BUILD)/asan/segment_unit
 
 # Race detection: the threaded host reference reducers / arg-reductions under
 # ThreadSanitizer (tests/native/race_unit.cpp; exits non-zero on any report).

@@ -24,6 +24,7 @@
 #include "mireduce/reduce_dim.hpp"
 #include "mireduce/reduce_many.hpp"
 #include "mireduce/scan.hpp"
+#include "mireduce/segment.hpp"
 #include "mireduce/trace.hpp"
 #include "mireduce/types.hpp"
 #include "mireduce/version.hpp"
@@ -625,6 +626,60 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"), py::arg("out_dtype"),
       py::arg("out_ptr"), py::arg("exclusive") = false, py::arg("carry_in_ptr") = 0, py::arg("carry_out_ptr") = 0);
+  // Ragged reductions (csrc/kernels/segment.hip, csrc/runtime/segment_cpu.cpp).
+  auto segment_plan_dict = [](const SegmentPlan& p) {
+    py::dict d;
+    d["block"] = p.block;
+    d["tile_elems"] = p.tile_elems;
+    d["tiles"] = p.tiles;
+    d["grid"] = p.grid;
+    d["span_grid"] = p.span_grid;
+    d["launches"] = p.launches;
+    return d;
+  };
+  py::class_<SegmentWorkspace, std::shared_ptr<SegmentWorkspace>>(m, "SegmentWorkspace")
+      .def(py::init<int, int64_t>(), py::arg("device") = -1, py::arg("max_tiles") = kSegmentDefaultTiles)
+      .def_property_readonly("device", &SegmentWorkspace::device)
+      .def_property_readonly("num_cus", &SegmentWorkspace::num_cus)
+      .def_property_readonly("max_tiles", &SegmentWorkspace::max_tiles);
+  m.def(
+      "segment_reduce",
+      [segment_plan_dict](SegmentWorkspace& ws, uintptr_t in, uint64_t n, int dtype, int op, int acc, uintptr_t offsets,
+                          uint64_t segments, uintptr_t out, uintptr_t stream, int max_blocks, int wg_per_cu) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && acc >= 0 && acc < kNumDTypes && op >= 0 && op < kNumOps,
+                         "dtype / op out of range");
+        SegmentConfig cfg;
+        cfg.max_blocks = max_blocks;
+        cfg.wg_per_cu = wg_per_cu;
+        return segment_plan_dict(segment_reduce(as_ptr<const void>(in), n, static_cast<DType>(dtype), static_cast<Op>(op),
+                                                static_cast<DType>(acc), as_ptr<const int64_t>(offsets), segments,
+                                                as_ptr<void>(out), ws, as_stream(stream), cfg));
+      },
+      py::arg("ws"), py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"),
+      py::arg("offsets_ptr"), py::arg("segments"), py::arg("out_ptr"), py::arg("stream") = 0,
+      py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0);
+  m.def(
+      "segment_plan",
+      [segment_plan_dict](uint64_t n, uint64_t segments, int dtype, int num_cus, int max_blocks, int wg_per_cu) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        SegmentConfig cfg;
+        cfg.max_blocks = max_blocks;
+        cfg.wg_per_cu = wg_per_cu;
+        return segment_plan_dict(plan_segment(n, segments, static_cast<DType>(dtype), cfg, num_cus));
+      },
+      py::arg("n"), py::arg("segments"), py::arg("dtype"), py::arg("num_cus") = 256, py::arg("max_blocks") = 0,
+      py::arg("wg_per_cu") = 0);
+  m.def(
+      "cpu_segment_reduce",
+      [](uintptr_t in, uint64_t n, int dtype, int op, int acc, uintptr_t offsets, uint64_t segments, uintptr_t out) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && acc >= 0 && acc < kNumDTypes && op >= 0 && op < kNumOps,
+                         "dtype / op out of range");
+        py::gil_scoped_release nogil;
+        cpu_segment_reduce(as_ptr<const void>(in), n, static_cast<DType>(dtype), static_cast<Op>(op),
+                           static_cast<DType>(acc), as_ptr<const int64_t>(offsets), segments, as_ptr<void>(out));
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"), py::arg("offsets_ptr"),
+      py::arg("segments"), py::arg("out_ptr"));
   m.def(
       "moments",
       [](uintptr_t in, uint64_t n, int dtype, uintptr_t out5, uintptr_t partials, int max_grid, int num_cus,
