@@ -23,6 +23,9 @@ struct DimPlan {
   int lanes_per_row = 64;   // rows mode: lanes cooperating on one row segment (1..64)
   uint64_t splits = 1;      // rows mode: segments per row (> 1: per-row tickets, last arriver folds)
                             // cols mode: row ranges per column block (> 1: second fold launch)
+  uint64_t seg_len = 0;     // rows mode: elements per row segment; cols mode: rows per row range
+  bool aligned = false;     // rows mode: whole-vector rows (16-byte base and row length); cols mode: vector layout
+  bool pipelined = false;   // rows mode: short aligned rows ran the two-batch pipelined loop
 };
 
 // Scratch (device bytes) a dimension reduction of this shape needs; 0 if none. The buffer must be

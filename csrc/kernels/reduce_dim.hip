@@ -461,13 +461,12 @@ int wg_cap(int occ, int preferred) {
 }
 
 // Aligned short rows: the two-batch pipelined loop (short_rows_kernel PIPE). MIREDUCE_DIM_SHORT_PIPE=0
-// selects the single-batch loop (A/B runs).
+// selects the single-batch loop (A/B runs, and the tests of that loop). Read at every launch, like
+// MIREDUCE_XCD_SKEW: a value cached at the first launch made a later setting in the same process a
+// silent no-op (and a first launch under =0 switched the pipelined loop off for good).
 bool short_pipe() {
-  static const bool on = [] {
-    const char* e = std::getenv("MIREDUCE_DIM_SHORT_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+  const char* e = std::getenv("MIREDUCE_DIM_SHORT_PIPE");
+  return !(e && e[0] == '0');
 }
 
 // Pipelined short rows: MIREDUCE_DIM_NT_OUT=1 writes the results with non-temporal stores (one
@@ -481,6 +480,9 @@ bool short_nt_out() {
   return on;
 }
 
+// Which short-row kernel launch_rows picks (DimPlan::pipelined reports it).
+bool rows_pipelined(const kern::RowArgs& a) { return a.lpr < 64 && a.aligned && short_pipe(); }
+
 using RowFn = void (*)(const kern::RowArgs&, int, hipStream_t);
 using OccFn = int (*)(bool);  // resident workgroups per CU of the (short-row | vector) variant
 using ColFn = void (*)(const kern::ColArgs&, dim3, bool, hipStream_t);
@@ -488,7 +490,7 @@ using FoldFn = void (*)(const void*, uint64_t, uint64_t, void*, hipStream_t);
 
 template <class OpT, class T, class AccT>
 void launch_rows(const kern::RowArgs& a, int grid, hipStream_t s) {
-  if (a.lpr < 64 && a.aligned && short_pipe())
+  if (rows_pipelined(a))
     hipLaunchKernelGGL((kern::short_rows_kernel<OpT, T, AccT, true, true>), dim3(grid), dim3(kern::kDimBlock), 0, s, a);
   else if (a.lpr < 64 && a.aligned)
     hipLaunchKernelGGL((kern::short_rows_kernel<OpT, T, AccT, true>), dim3(grid), dim3(kern::kDimBlock), 0, s, a);
@@ -600,9 +602,14 @@ size_t reduce_rows_scratch_bytes(size_t rows, size_t cols, DType t, int num_cus)
 }
 
 size_t reduce_cols_scratch_bytes(size_t outer, size_t rows, size_t cols, DType t, DType acc, int num_cus) {
-  // An aligned base (vector layout: fewer threads, so the most row splits) bounds every base.
-  const ColLayout L = col_layout(nullptr, outer, rows, cols, t, num_cus);
-  return L.splits > 1 ? L.splits * outer * cols * dtype_size(acc) : 0;
+  // The bound covers both layouts, whatever the base's alignment turns out to be: the vector layout
+  // has fewer workgroups per slab (more row ranges fit the grid), the one-column layout fewer row
+  // groups per workgroup (more row ranges fit the rows: a misaligned [8192, 128] bf16 slab is cut into
+  // 256 ranges where the vector layout's 32 were reserved, and [257, 64] into 5 where none was).
+  const ColLayout v = col_layout(nullptr, outer, rows, cols, t, num_cus);
+  const ColLayout s = col_layout(reinterpret_cast<const void*>(uintptr_t{1}), outer, rows, cols, t, num_cus);
+  const uint64_t splits = std::max(v.splits, s.splits);
+  return splits > 1 ? splits * outer * cols * dtype_size(acc) : 0;
 }
 
 DimPlan reduce_rows(const void* in, size_t rows, size_t cols, DType t, Op op, DType acc, void* out,
@@ -636,6 +643,9 @@ DimPlan reduce_rows(const void* in, size_t rows, size_t cols, DType t, Op op, DT
   plan.grid = L.grid;
   plan.lanes_per_row = L.lpr;
   plan.splits = L.splits;
+  plan.seg_len = L.seg_len;
+  plan.aligned = a.aligned != 0;
+  plan.pipelined = rows_pipelined(a);
   return plan;
 }
 
@@ -675,6 +685,8 @@ DimPlan reduce_cols(const void* in, size_t outer, size_t rows, size_t cols, DTyp
   }
   plan.grid = static_cast<int>(std::min<uint64_t>(INT32_MAX, static_cast<uint64_t>(std::max(L.blocks, 1)) * L.splits * outer));
   plan.splits = L.splits;
+  plan.seg_len = L.rows_per_split;
+  plan.aligned = L.vec;
   plan.lanes_per_row = L.vec ? static_cast<int>(16 / dtype_size(t)) : 1;
   return plan;
 }

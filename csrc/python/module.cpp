@@ -465,6 +465,9 @@ PYBIND11_MODULE(_C, m) {
     d["block"] = p.block;
     d["lanes_per_row"] = p.lanes_per_row;
     d["splits"] = p.splits;
+    d["seg_len"] = p.seg_len;
+    d["aligned"] = p.aligned;
+    d["pipelined"] = p.pipelined;
     return d;
   };
   m.def(
