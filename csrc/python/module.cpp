@@ -17,6 +17,7 @@
 #include "mireduce/cpu_reference.hpp"
 #include "mireduce/direct.hpp"
 #include "mireduce/final_line.hpp"
+#include "mireduce/histogram.hpp"
 #include "mireduce/ladder.hpp"
 #include "mireduce/moments.hpp"
 #include "mireduce/mt19937.hpp"
@@ -683,6 +684,70 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"), py::arg("offsets_ptr"),
       py::arg("segments"), py::arg("out_ptr"));
+  // Histograms (csrc/kernels/histogram.hip, csrc/runtime/histogram_cpu.cpp).
+  auto histogram_plan_dict = [](const HistogramPlan& p) {
+    py::dict d;
+    d["path"] = p.path == HistogramPath::Lds ? "lds" : "global";
+    d["block"] = p.block;
+    d["grid"] = p.grid;
+    d["replicas"] = p.replicas;
+    d["lds_bytes"] = p.lds_bytes;
+    d["flush_elems"] = p.flush_elems;
+    d["tile_elems"] = p.tile_elems;
+    d["tiles"] = p.tiles;
+    d["lds_bins"] = p.lds_bins;
+    return d;
+  };
+  auto histogram_cfg = [](int max_blocks, int wg_per_cu, int64_t lds_bins, int replicas, uint64_t flush_elems,
+                          bool fold = false, uintptr_t partials = 0, uint64_t partials_bytes = 0) {
+    HistogramConfig cfg;
+    cfg.fold = fold;
+    cfg.partials = as_ptr<void>(partials);
+    cfg.partials_bytes = partials_bytes;
+    cfg.max_blocks = max_blocks;
+    cfg.wg_per_cu = wg_per_cu;
+    cfg.lds_bins = lds_bins;
+    cfg.replicas = replicas;
+    cfg.flush_elems = flush_elems;
+    return cfg;
+  };
+  m.def(
+      "histogram",
+      [histogram_plan_dict, histogram_cfg](uintptr_t in, uint64_t n, int dtype, int64_t bins, double lo, double hi,
+                                           uintptr_t out, uintptr_t dropped, bool accumulate, uintptr_t stream,
+                                           int max_blocks, int wg_per_cu, int64_t lds_bins, int replicas,
+                                           uint64_t flush_elems, bool fold, uintptr_t partials, uint64_t partials_bytes) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return histogram_plan_dict(histogram(as_ptr<const void>(in), n, static_cast<DType>(dtype), bins, lo, hi,
+                                             as_ptr<int64_t>(out), as_ptr<int64_t>(dropped), accumulate, as_stream(stream),
+                                             histogram_cfg(max_blocks, wg_per_cu, lds_bins, replicas, flush_elems, fold,
+                                                           partials, partials_bytes)));
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("bins"), py::arg("lo"), py::arg("hi"),
+      py::arg("out_ptr"), py::arg("dropped_ptr"), py::arg("accumulate") = false, py::arg("stream") = 0,
+      py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0, py::arg("lds_bins") = 0, py::arg("replicas") = 0,
+      py::arg("flush_elems") = 0, py::arg("fold") = false, py::arg("partials_ptr") = 0, py::arg("partials_bytes") = 0);
+  m.def(
+      "histogram_plan",
+      [histogram_plan_dict, histogram_cfg](uint64_t n, int64_t bins, int dtype, int num_cus, int max_blocks, int wg_per_cu,
+                                           int64_t lds_bins, int replicas, uint64_t flush_elems) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return histogram_plan_dict(plan_histogram(n, bins, static_cast<DType>(dtype),
+                                                  histogram_cfg(max_blocks, wg_per_cu, lds_bins, replicas, flush_elems), num_cus));
+      },
+      py::arg("n"), py::arg("bins"), py::arg("dtype"), py::arg("num_cus") = 256, py::arg("max_blocks") = 0,
+      py::arg("wg_per_cu") = 0, py::arg("lds_bins") = 0, py::arg("replicas") = 0, py::arg("flush_elems") = 0);
+  m.def(
+      "cpu_histogram",
+      [](uintptr_t in, uint64_t n, int dtype, int64_t bins, double lo, double hi, uintptr_t out, uintptr_t dropped,
+         bool accumulate) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        py::gil_scoped_release nogil;
+        cpu_histogram(as_ptr<const void>(in), n, static_cast<DType>(dtype), bins, lo, hi, as_ptr<int64_t>(out),
+                      as_ptr<int64_t>(dropped), accumulate);
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("bins"), py::arg("lo"), py::arg("hi"),
+      py::arg("out_ptr"), py::arg("dropped_ptr"), py::arg("accumulate") = false);
   m.def(
       "moments",
       [](uintptr_t in, uint64_t n, int dtype, uintptr_t out5, uintptr_t partials, int max_grid, int num_cus,

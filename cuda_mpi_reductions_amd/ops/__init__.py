@@ -11,3 +11,4 @@ from .reduce_many import ReduceMany, norm_many, reduce_many  # noqa: F401
 from .arg_reduce import arg_reduce, argmax, argmin  # noqa: F401
 from .scan import ScanConfig, cummax, cummin, cumsum, scan, scan_plan, scan_workspace  # noqa: F401
 from .segment import SegmentConfig, segment_plan, segment_reduce, segment_workspace  # noqa: F401
+from .histogram import HistogramConfig, bincount, histc, histogram_plan  # noqa: F401
