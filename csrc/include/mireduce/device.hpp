@@ -1,4 +1,4 @@
-// Device helpers: properties, hipEvent timing, RAII device buffers.
+// Device helpers: properties, hipEvent timing, RAII device buffers and current-device guard.
 //
 // Reference: cutilDeviceInit / cudaChooseDevice / cudaGetDeviceProperties (reduction.cpp:130-155,
 // cutil_inline_runtime.h:388-417) and the cutil timers. Device-side intervals are measured with
@@ -38,6 +38,22 @@ class EventTimer {
 
  private:
   hipEvent_t a_ = nullptr, b_ = nullptr;
+};
+
+// Makes `device` the current device (a negative one: keeps the current device) and restores the
+// previous one when the scope ends, on every exit path.
+class DeviceGuard {
+ public:
+  explicit DeviceGuard(int device) {
+    MIREDUCE_HIP_THROW(hipGetDevice(&prev_));
+    if (device >= 0) MIREDUCE_HIP_THROW(hipSetDevice(device));
+  }
+  ~DeviceGuard() { (void)hipSetDevice(prev_); }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+
+ private:
+  int prev_ = 0;
 };
 
 class DeviceBuffer {

@@ -93,6 +93,15 @@ template <> struct is_half16<bf16_t> { static constexpr bool value = true; };
 template <> struct is_half16<f16_t> { static constexpr bool value = true; };
 template <class T> inline constexpr bool is_half16_v = is_half16<T>::value;
 
+// An accumulator value in the element (or output) type T: int64 -> int32 wraps, fp64 -> fp32 and
+// fp32 -> 16-bit round to nearest even.
+template <class T, class AccT>
+MIREDUCE_HD T from_acc(AccT v) {
+  if constexpr (std::is_same_v<T, AccT>) return v;
+  else if constexpr (is_half16_v<T>) return T::from_float(v);
+  else return static_cast<T>(v);
+}
+
 // Significand bits (incl. the implicit one): uniform fills use exactly this many random bits so
 // every generated value is representable.
 template <class T> struct half_precision;

@@ -25,6 +25,7 @@
 
 #include "mireduce/arg_reduce.hpp"
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/vec16.hpp"
 
@@ -667,14 +668,8 @@ constexpr ArgEntry arg_entry() {
 
 template <bool MAX>
 ArgEntry arg_lookup_dtype(DType t) {
-  switch (t) {
-    case DType::Int32: return arg_entry<MAX, int32_t>();
-    case DType::Int64: return arg_entry<MAX, int64_t>();
-    case DType::Float32: return arg_entry<MAX, float>();
-    case DType::Float64: return arg_entry<MAX, double>();
-    case DType::BFloat16: return arg_entry<MAX, bf16_t>();
-    case DType::Float16: return arg_entry<MAX, f16_t>();
-  }
+  ArgEntry e{};
+  if (visit_dtype(t, [&](auto z) { e = arg_entry<MAX, decltype(z)>(); })) return e;
   throw Error("arg_reduce: unsupported element type");
 }
 
@@ -775,14 +770,7 @@ ArgPlan arg_reduce_rows(const void* in, size_t rows, size_t cols, DType t, Op op
 void loc_pack(const void* value, const int64_t* index, int64_t index_offset, DType t, uint64_t* pair,
               hipStream_t stream) {
   MIREDUCE_REQUIRE(value != nullptr && index != nullptr && pair != nullptr, "loc_pack: null pointer");
-  switch (t) {
-    case DType::Int32: launch_loc_pack<int32_t>(value, index, index_offset, pair, stream); break;
-    case DType::Int64: launch_loc_pack<int64_t>(value, index, index_offset, pair, stream); break;
-    case DType::Float32: launch_loc_pack<float>(value, index, index_offset, pair, stream); break;
-    case DType::Float64: launch_loc_pack<double>(value, index, index_offset, pair, stream); break;
-    case DType::BFloat16: launch_loc_pack<bf16_t>(value, index, index_offset, pair, stream); break;
-    case DType::Float16: launch_loc_pack<f16_t>(value, index, index_offset, pair, stream); break;
-  }
+  visit_dtype(t, [&](auto z) { launch_loc_pack<decltype(z)>(value, index, index_offset, pair, stream); });
   MIREDUCE_HIP_THROW(hipGetLastError());
 }
 
@@ -791,14 +779,7 @@ void loc_pick(const uint64_t* pairs, int world, DType t, Op op, int64_t* out_ind
   MIREDUCE_REQUIRE(op == Op::Max || op == Op::Min, "loc_pick: the operator must be MAX or MIN");
   MIREDUCE_REQUIRE(world >= 1 && pairs != nullptr && out_index != nullptr, "loc_pick: bad arguments");
   const bool mx = op == Op::Max;
-  switch (t) {
-    case DType::Int32: launch_loc_pick<int32_t>(pairs, world, mx, out_index, out_value, stream); break;
-    case DType::Int64: launch_loc_pick<int64_t>(pairs, world, mx, out_index, out_value, stream); break;
-    case DType::Float32: launch_loc_pick<float>(pairs, world, mx, out_index, out_value, stream); break;
-    case DType::Float64: launch_loc_pick<double>(pairs, world, mx, out_index, out_value, stream); break;
-    case DType::BFloat16: launch_loc_pick<bf16_t>(pairs, world, mx, out_index, out_value, stream); break;
-    case DType::Float16: launch_loc_pick<f16_t>(pairs, world, mx, out_index, out_value, stream); break;
-  }
+  visit_dtype(t, [&](auto z) { launch_loc_pick<decltype(z)>(pairs, world, mx, out_index, out_value, stream); });
   MIREDUCE_HIP_THROW(hipGetLastError());
 }
 

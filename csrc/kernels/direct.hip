@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "mireduce/check.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/direct.hpp"
 #include "mireduce/peer.hpp"
 #include "mireduce/ops.hpp"
@@ -223,15 +224,6 @@ void direct_chunk(size_t count, size_t elem_size, int world, int r, size_t* begi
 }
 
 namespace {
-
-struct DeviceGuard {
-  int prev = 0;
-  explicit DeviceGuard(int dev) {
-    MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-    MIREDUCE_HIP_THROW(hipSetDevice(dev));
-  }
-  ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
 
 constexpr size_t kSigBytes = static_cast<size_t>(kDirectPhases) * kMaxDirectBlocks * kMaxDirectRanks * sizeof(unsigned);
 

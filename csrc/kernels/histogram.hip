@@ -27,9 +27,11 @@
 #include <type_traits>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/histogram.hpp"
 #include "mireduce/vec16.hpp"
+#include "tile_load.hpp"
 
 namespace mireduce {
 namespace kern {
@@ -235,17 +237,17 @@ HistogramPlan histogram(const void* in, uint64_t n, DType t, int64_t bins, doubl
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(out) % 8 == 0 && reinterpret_cast<uintptr_t>(dropped) % 8 == 0,
                    "histogram: out / dropped must be 8-byte aligned");
   const int cus = cus_of_current_device();
-  const uint64_t pad = (reinterpret_cast<uintptr_t>(in) % 16) / es;
-  HistogramPlan p = plan_histogram(n ? pad + n : 0, bins, t, cfg, cus);
+  const kern::TileSpan sp = kern::tile_span(in, n, es);
+  HistogramPlan p = plan_histogram(n ? sp.end : 0, bins, t, cfg, cus);
   if (!accumulate) {
     MIREDUCE_HIP_THROW(hipMemsetAsync(out, 0, static_cast<size_t>(bins) * 8, stream));
     MIREDUCE_HIP_THROW(hipMemsetAsync(dropped, 0, 8, stream));
   }
   if (n == 0) return p;
   kern::HistArgs a{};
-  a.vin = static_cast<const char*>(in) - pad * es;
-  a.pad = pad;
-  a.end = pad + n;
+  a.vin = sp.vin;
+  a.pad = sp.pad;
+  a.end = sp.end;
   a.tiles = p.tiles;
   a.bins = bins;
   a.lo = lo;
@@ -260,14 +262,7 @@ HistogramPlan histogram(const void* in, uint64_t n, DType t, int64_t bins, doubl
                      "histogram: fold needs partials of at least grid * bins * 8 bytes");
     a.partials = static_cast<unsigned long long*>(cfg.partials);
   }
-  switch (t) {
-    case DType::Int32: launch_typed<int32_t>(a, p, stream); break;
-    case DType::Int64: launch_typed<int64_t>(a, p, stream); break;
-    case DType::Float32: launch_typed<float>(a, p, stream); break;
-    case DType::Float64: launch_typed<double>(a, p, stream); break;
-    case DType::BFloat16: launch_typed<bf16_t>(a, p, stream); break;
-    case DType::Float16: launch_typed<f16_t>(a, p, stream); break;
-  }
+  visit_dtype(t, [&](auto z) { launch_typed<decltype(z)>(a, p, stream); });
   MIREDUCE_HIP_THROW(hipGetLastError());
   return p;
 }

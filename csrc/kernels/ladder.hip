@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/ladder.hpp"
 #include "mireduce/ops.hpp"
 
@@ -255,40 +256,14 @@ LadderPasses ladder_reduce_passes(int kernel, const void* in, uint64_t n, DType 
   MIREDUCE_REQUIRE(!dtype_is_half(t), "ladder kernels 0..6 cover the reference's element types (int, float, double, "
                                       "int64); bf16/half use the streaming kernel (7/8)");
   using namespace ladder;
-#define MIREDUCE_LADDER_CASE(OPT, T, A) \
-  return run<OPT, T, A>(kernel, in, n, out, scratch, max_threads, max_blocks, cpu_thresh, cpu_final, s)
-  switch (op) {
-    case Op::Sum:
-      switch (t) {
-        case DType::Int32: if (acc == DType::Int64) MIREDUCE_LADDER_CASE(SumOp, int32_t, int64_t); MIREDUCE_LADDER_CASE(SumOp, int32_t, int32_t);
-        case DType::Int64: MIREDUCE_LADDER_CASE(SumOp, int64_t, int64_t);
-        case DType::Float32: if (acc == DType::Float64) MIREDUCE_LADDER_CASE(SumOp, float, double); MIREDUCE_LADDER_CASE(SumOp, float, float);
-        case DType::Float64: MIREDUCE_LADDER_CASE(SumOp, double, double);
-        default: break;
-      }
-      break;
-    case Op::Min:
-      switch (t) {
-        case DType::Int32: MIREDUCE_LADDER_CASE(MinOp, int32_t, int32_t);
-        case DType::Int64: MIREDUCE_LADDER_CASE(MinOp, int64_t, int64_t);
-        case DType::Float32: MIREDUCE_LADDER_CASE(MinOp, float, float);
-        case DType::Float64: MIREDUCE_LADDER_CASE(MinOp, double, double);
-        default: break;
-      }
-      break;
-    default:
-      break;
-    case Op::Max:
-      switch (t) {
-        case DType::Int32: MIREDUCE_LADDER_CASE(MaxOp, int32_t, int32_t);
-        case DType::Int64: MIREDUCE_LADDER_CASE(MaxOp, int64_t, int64_t);
-        case DType::Float32: MIREDUCE_LADDER_CASE(MaxOp, float, float);
-        case DType::Float64: MIREDUCE_LADDER_CASE(MaxOp, double, double);
-        default: break;
-      }
-      break;
-  }
-#undef MIREDUCE_LADDER_CASE
+  LadderPasses r;
+  if (visit_combo<PlainOps>(op, t, acc, [&](auto c) {
+        using C = decltype(c);
+        if constexpr (!is_half16_v<typename C::elem>)
+          r = run<typename C::op, typename C::elem, typename C::acc>(kernel, in, n, out, scratch, max_threads, max_blocks,
+                                                                     cpu_thresh, cpu_final, s);
+      }))
+    return r;
   throw Error("ladder: unsupported combination");
 }
 

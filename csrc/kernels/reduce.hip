@@ -2,6 +2,7 @@
 // reduce_tab_*.hip translation units), single-/two-pass launches, bound (prepared) launches and
 // the two-pass finalize / element-wise combine kernels. The kernel templates and their design
 // notes live in reduce_kernels.hpp.
+#include "mireduce/device.hpp"
 #include "reduce_kernels.hpp"
 
 namespace mireduce {
@@ -19,45 +20,6 @@ int block_index(int b) { return b == 256 ? 0 : (b == 512 ? 1 : (b == 1024 ? 2 : 
 int body_index(const LaunchPlan& p) { return p.window == 2 ? 1 : (p.window == 4 ? 2 : 0); }
 int unroll_index(int u) { return u == 2 ? 0 : (u == 4 ? 1 : (u == 8 ? 2 : (u == 16 ? 3 : -1))); }
 
-// combo index: (op, dtype, acc) → 0..28
-int combo_index(Op op, DType t, DType acc) {
-  if (op == Op::SumSq) {  // 20..24
-    switch (t) {
-      case DType::Float32: return acc == DType::Float64 ? 20 : (acc == DType::Float32 ? 21 : -1);
-      case DType::Float64: return acc == DType::Float64 ? 22 : -1;
-      case DType::BFloat16: return acc == DType::Float32 ? 23 : -1;
-      case DType::Float16: return acc == DType::Float32 ? 24 : -1;
-      default: return -1;
-    }
-  }
-  if (op == Op::AbsMax) {  // 25..28
-    switch (t) {
-      case DType::Float32: return acc == DType::Float32 ? 25 : -1;
-      case DType::Float64: return acc == DType::Float64 ? 26 : -1;
-      case DType::BFloat16: return acc == DType::Float32 ? 27 : -1;
-      case DType::Float16: return acc == DType::Float32 ? 28 : -1;
-      default: return -1;
-    }
-  }
-  const int o = static_cast<int>(op);
-  switch (t) {
-    case DType::Int32:
-      if (op == Op::Sum) return acc == DType::Int64 ? 0 : (acc == DType::Int32 ? 1 : -1);
-      return acc == DType::Int32 ? 1 + o : -1;  // 2 (min), 3 (max)
-    case DType::Int64:
-      return acc == DType::Int64 ? 4 + o : -1;  // 4..6
-    case DType::Float32:
-      if (op == Op::Sum) return acc == DType::Float64 ? 7 : (acc == DType::Float32 ? 8 : -1);
-      return acc == DType::Float32 ? 8 + o : -1;  // 9 (min), 10 (max)
-    case DType::Float64:
-      return acc == DType::Float64 ? 11 + o : -1;  // 11..13
-    case DType::BFloat16:
-      return acc == DType::Float32 ? 14 + o : -1;  // 14..16
-    case DType::Float16:
-      return acc == DType::Float32 ? 17 + o : -1;  // 17..19
-  }
-  return -1;
-}
 const Table& table() {
   static const Table tb = [] {
     Table t{};
@@ -224,9 +186,7 @@ Workspace::Workspace(int device, int max_grid, SlotMemory slot_memory) : max_gri
   int cus = 0;
   MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
   num_cus_ = cus > 0 ? cus : 256;
-  int prev = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-  MIREDUCE_HIP_THROW(hipSetDevice(device));
+  const DeviceGuard guard(device);
   MIREDUCE_HIP_THROW(hipMalloc(&partials_, static_cast<size_t>(max_grid) * 8));
   // polled fan-in slots: uncached, so the finisher's polls see every XCD's stores. SlotMemory::Coarse
   // (experiments only, tools/launch_floor.hip): ordinary device memory instead, relying on the
@@ -238,7 +198,6 @@ Workspace::Workspace(int device, int max_grid, SlotMemory slot_memory) : max_gri
   MIREDUCE_HIP_THROW(hipExtMallocWithFlags(reinterpret_cast<void**>(&fan_), 256, flags));
   MIREDUCE_HIP_THROW(hipMemset(fan_, 0, 256));
   MIREDUCE_HIP_THROW(hipDeviceSynchronize());
-  MIREDUCE_HIP_THROW(hipSetDevice(prev));
 }
 
 Workspace::~Workspace() {
@@ -249,12 +208,8 @@ Workspace::~Workspace() {
 
 unsigned Workspace::error() const {
   unsigned v = 0;
-  int prev = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-  MIREDUCE_HIP_THROW(hipSetDevice(device_));
-  const hipError_t e = hipMemcpy(&v, fan_ + 1, sizeof v, hipMemcpyDeviceToHost);
-  (void)hipSetDevice(prev);
-  MIREDUCE_HIP_THROW(e);
+  const DeviceGuard guard(device_);
+  MIREDUCE_HIP_THROW(hipMemcpy(&v, fan_ + 1, sizeof v, hipMemcpyDeviceToHost));
   return v;
 }
 

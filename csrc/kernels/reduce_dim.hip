@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/reduce_dim.hpp"
@@ -545,43 +546,15 @@ constexpr DimEntry entry() {
           rows_resident<OpT, T, AccT>, cols_resident<OpT, T, AccT>};
 }
 
-// (op, dtype, acc) -> kernels; the same 20 combinations as the full reduction.
+// (op, dtype, acc) -> kernels, for every listed combination (combo.hpp).
 DimEntry lookup(Op op, DType t, DType acc) {
   MIREDUCE_REQUIRE(acc_supported(t, op, acc), "unsupported (dtype, op, accumulator) combination");
-#define MIREDUCE_DIM(OPV, OPT)                                                                        \
-  if (op == OPV) {                                                                                    \
-    switch (t) {                                                                                      \
-      case DType::Int32: return acc == DType::Int64 ? entry<OPT, int32_t, int64_t>() : entry<OPT, int32_t, int32_t>(); \
-      case DType::Int64: return entry<OPT, int64_t, int64_t>();                                       \
-      case DType::Float32: return acc == DType::Float64 ? entry<OPT, float, double>() : entry<OPT, float, float>(); \
-      case DType::Float64: return entry<OPT, double, double>();                                       \
-      case DType::BFloat16: return entry<OPT, bf16_t, float>();                                       \
-      case DType::Float16: return entry<OPT, f16_t, float>();                                         \
-    }                                                                                                 \
-  }
-  MIREDUCE_DIM(Op::Sum, SumOp)
-  MIREDUCE_DIM(Op::Min, MinOp)
-  MIREDUCE_DIM(Op::Max, MaxOp)
-#undef MIREDUCE_DIM
-  // fused ops: floating types only (acc_supported)
-  if (op == Op::SumSq) {
-    switch (t) {
-      case DType::Float32: return acc == DType::Float64 ? entry<SumSqOp, float, double>() : entry<SumSqOp, float, float>();
-      case DType::Float64: return entry<SumSqOp, double, double>();
-      case DType::BFloat16: return entry<SumSqOp, bf16_t, float>();
-      case DType::Float16: return entry<SumSqOp, f16_t, float>();
-      default: break;
-    }
-  }
-  if (op == Op::AbsMax) {
-    switch (t) {
-      case DType::Float32: return entry<AbsMaxOp, float, float>();
-      case DType::Float64: return entry<AbsMaxOp, double, double>();
-      case DType::BFloat16: return entry<AbsMaxOp, bf16_t, float>();
-      case DType::Float16: return entry<AbsMaxOp, f16_t, float>();
-      default: break;
-    }
-  }
+  DimEntry e{};
+  if (visit_combo(op, t, acc, [&](auto c) {
+        using C = decltype(c);
+        e = entry<typename C::op, typename C::elem, typename C::acc>();
+      }))
+    return e;
   throw Error("reduce_dim: unsupported combination");
 }
 

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/vec16.hpp"
@@ -828,8 +829,6 @@ constexpr int kUnrolls[] = {2, 4, 8, 16};
 constexpr int kNumBlocks = 3;
 constexpr int kNumUnrolls = 4;
 
-constexpr int kCombos = 29;
-
 // Body schedules: 0 = hipcc's own schedule of the plain loop, 1 / 2 = explicit load window of 2 / 4
 // registers per thread (stream_window_seq; nt only).
 constexpr int kNumBodies = 3;
@@ -859,22 +858,25 @@ void fill_block(Table& tb, int c) {
   fill_one<OpT, T, AccT, BI, 3>(tb, c);
 }
 
+// A combination's table row is its position in combo.hpp's list.
 template <class OpT, class T, class AccT>
-void fill_combo(Table& tb, int c) {
+void fill_combo(Table& tb) {
+  constexpr int c = combo_position<OpT, T, AccT>;
+  static_assert(c >= 0, "not a listed (op, dtype, acc) combination");
   fill_block<OpT, T, AccT, 0>(tb, c);
   fill_block<OpT, T, AccT, 1>(tb, c);
   fill_block<OpT, T, AccT, 2>(tb, c);
 }
 
-// One filler per TU (reduce_tab_<group>.hip): sets tb.fn[c] for its combos c.
-void fill_table_int32(Table& tb);  // combos 0..3
-void fill_table_int64(Table& tb);  // combos 4..6
-void fill_table_f32(Table& tb);  // combos 7..10
-void fill_table_f64(Table& tb);  // combos 11..13
-void fill_table_bf16(Table& tb);  // combos 14..16
-void fill_table_f16(Table& tb);  // combos 17..19
-void fill_table_sumsq(Table& tb);  // combos 20..24
-void fill_table_absmax(Table& tb);  // combos 25..28
+// One filler per TU (reduce_tab_<group>.hip): fills tb.fn[c] for its combinations.
+void fill_table_int32(Table& tb);
+void fill_table_int64(Table& tb);
+void fill_table_f32(Table& tb);
+void fill_table_f64(Table& tb);
+void fill_table_bf16(Table& tb);
+void fill_table_f16(Table& tb);
+void fill_table_sumsq(Table& tb);
+void fill_table_absmax(Table& tb);
 
 }  // namespace detail
 }  // namespace mireduce

@@ -16,6 +16,8 @@
 #include <vector>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/reduce_many.hpp"
@@ -171,39 +173,12 @@ constexpr ManyEntry many_entry() {
 
 ManyEntry many_lookup(Op op, DType t, DType acc) {
   MIREDUCE_REQUIRE(acc_supported(t, op, acc), "unsupported (dtype, op, accumulator) combination");
-#define MIREDUCE_MANY(OPV, OPT)                                                                          \
-  if (op == OPV) {                                                                                       \
-    switch (t) {                                                                                         \
-      case DType::Int32: return acc == DType::Int64 ? many_entry<OPT, int32_t, int64_t>() : many_entry<OPT, int32_t, int32_t>(); \
-      case DType::Int64: return many_entry<OPT, int64_t, int64_t>();                                     \
-      case DType::Float32: return acc == DType::Float64 ? many_entry<OPT, float, double>() : many_entry<OPT, float, float>(); \
-      case DType::Float64: return many_entry<OPT, double, double>();                                     \
-      case DType::BFloat16: return many_entry<OPT, bf16_t, float>();                                     \
-      case DType::Float16: return many_entry<OPT, f16_t, float>();                                       \
-    }                                                                                                    \
-  }
-  MIREDUCE_MANY(Op::Sum, SumOp)
-  MIREDUCE_MANY(Op::Min, MinOp)
-  MIREDUCE_MANY(Op::Max, MaxOp)
-#undef MIREDUCE_MANY
-  if (op == Op::SumSq) {
-    switch (t) {
-      case DType::Float32: return acc == DType::Float64 ? many_entry<SumSqOp, float, double>() : many_entry<SumSqOp, float, float>();
-      case DType::Float64: return many_entry<SumSqOp, double, double>();
-      case DType::BFloat16: return many_entry<SumSqOp, bf16_t, float>();
-      case DType::Float16: return many_entry<SumSqOp, f16_t, float>();
-      default: break;
-    }
-  }
-  if (op == Op::AbsMax) {
-    switch (t) {
-      case DType::Float32: return many_entry<AbsMaxOp, float, float>();
-      case DType::Float64: return many_entry<AbsMaxOp, double, double>();
-      case DType::BFloat16: return many_entry<AbsMaxOp, bf16_t, float>();
-      case DType::Float16: return many_entry<AbsMaxOp, f16_t, float>();
-      default: break;
-    }
-  }
+  ManyEntry e{};
+  if (visit_combo(op, t, acc, [&](auto c) {
+        using C = decltype(c);
+        e = many_entry<typename C::op, typename C::elem, typename C::acc>();
+      }))
+    return e;
   throw Error("reduce_many: unsupported combination");
 }
 
@@ -250,9 +225,7 @@ BoundReduceMany::BoundReduceMany(const std::vector<const void*>& ptrs, const std
   }
   MIREDUCE_REQUIRE(segs.size() < (1ull << 31), "reduce_many: too many segments");
   segments_ = segs.size();
-  int prev = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-  if (device >= 0) MIREDUCE_HIP_THROW(hipSetDevice(device));
+  const DeviceGuard guard(device);
   const size_t seg_bytes = segs.size() * sizeof(kern::Seg);
   const size_t info_off = (seg_bytes + 255) / 256 * 256;
   const size_t table_bytes = info_off + info.size() * sizeof(kern::TensorInfo);
@@ -269,7 +242,6 @@ BoundReduceMany::BoundReduceMany(const std::vector<const void*>& ptrs, const std
     resident = std::min(resident, std::atoi(e));
   const uint64_t blocks = segs.size();
   grid_ = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(blocks, static_cast<uint64_t>(num_cus) * resident)));
-  MIREDUCE_HIP_THROW(hipSetDevice(prev));
 }
 
 BoundReduceMany::~BoundReduceMany() {

@@ -37,11 +37,14 @@
 #include <type_traits>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/scan.hpp"
 #include "mireduce/vec16.hpp"
 #include "reduce_kernels.hpp"
+#include "tile_load.hpp"
 
 namespace mireduce {
 namespace kern {
@@ -80,13 +83,6 @@ struct ScanArgs {
   int out_vec;            // vout is 16-byte aligned: whole vectors are stored 16 bytes at a time
 };
 
-template <class OutT, class AccT>
-__device__ __forceinline__ OutT to_out(AccT v) {
-  if constexpr (std::is_same_v<OutT, AccT>) return v;
-  else if constexpr (is_half16_v<OutT>) return OutT::from_float(v);
-  else return static_cast<OutT>(v);  // int64 -> int32 wraps, fp64 -> fp32 rounds
-}
-
 template <class OpT, class AccT>
 __device__ __forceinline__ AccT wave_scan(AccT v) {
   const int lane = threadIdx.x & 63;
@@ -108,28 +104,12 @@ struct TileRegs {
   __device__ __forceinline__ static uint64_t vec_index(uint64_t tile, int u) {
     return tile * kScanTileVecs + static_cast<uint64_t>(u) * kScanBlock + threadIdx.x;
   }
-  __device__ __forceinline__ static bool whole(const ScanArgs& a, uint64_t v) {
-    return v * N >= a.pad && (v + 1) * N <= a.end;
-  }
+  __device__ __forceinline__ static TileSpan span(const ScanArgs& a) { return {a.vin, a.pad, a.end}; }
 
   __device__ __forceinline__ void load(const ScanArgs& a, uint64_t tile) {
-    const T ident = to_out<T>(OpT::template identity<AccT>());
+    const T ident = from_acc<T>(OpT::template identity<AccT>());
 #pragma unroll
-    for (int u = 0; u < kScanVectors; ++u) {
-      const uint64_t v = vec_index(tile, u);
-      if (whole(a, v)) {
-        raw[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(a.vin + v * 16));
-      } else {
-        alignas(16) T tmp[N];
-        const T* p = reinterpret_cast<const T*>(a.vin + v * 16);
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const uint64_t j = v * N + k;
-          tmp[k] = (j >= a.pad && j < a.end) ? p[k] : ident;
-        }
-        __builtin_memcpy(&raw[u], tmp, 16);
-      }
-    }
+    for (int u = 0; u < kScanVectors; ++u) load_clipped<T>(span(a), vec_index(tile, u), ident, raw[u]);
   }
 
   __device__ __forceinline__ AccT fold(int u) const {
@@ -181,10 +161,10 @@ __device__ __forceinline__ void tile_store(const ScanArgs& a, uint64_t tile, con
     for (int k = 0; k < N; ++k) {
       const AccT prev = run;
       run = OpT::apply(run, elem<T, AccT>(r.raw[u], k));
-      o[k] = to_out<OutT>(bad ? poisoned<OpT, AccT>() : (a.exclusive ? prev : run));
+      o[k] = from_acc<OutT>(bad ? poisoned<OpT, AccT>() : (a.exclusive ? prev : run));
     }
     OutT* dst = reinterpret_cast<OutT*>(a.vout + v * (sizeof(OutT) * N));
-    if (a.out_vec && TileRegs<OpT, T, AccT>::whole(a, v)) {
+    if (a.out_vec && whole<N>(TileRegs<OpT, T, AccT>::span(a), v)) {
       W w[kOutVecs];
       __builtin_memcpy(w, o, sizeof(o));
 #pragma unroll
@@ -446,33 +426,12 @@ void launch_out(DType t, DType out_t, const kern::ScanArgs& a, const Launch& l) 
   }
 }
 
-template <class OpT>
-void launch_op(DType t, DType acc, DType out_t, const kern::ScanArgs& a, const Launch& l) {
-  switch (t) {
-    case DType::Int32:
-      if (acc == DType::Int32) return launch_out<OpT, int32_t, int32_t>(t, out_t, a, l);
-      if constexpr (std::is_same_v<OpT, SumOp>) return launch_out<OpT, int32_t, int64_t>(t, out_t, a, l);
-      break;
-    case DType::Int64: return launch_out<OpT, int64_t, int64_t>(t, out_t, a, l);
-    case DType::Float32:
-      if (acc == DType::Float32) return launch_out<OpT, float, float>(t, out_t, a, l);
-      if constexpr (std::is_same_v<OpT, SumOp>) return launch_out<OpT, float, double>(t, out_t, a, l);
-      break;
-    case DType::Float64: return launch_out<OpT, double, double>(t, out_t, a, l);
-    case DType::BFloat16: return launch_out<OpT, bf16_t, float>(t, out_t, a, l);
-    case DType::Float16: return launch_out<OpT, f16_t, float>(t, out_t, a, l);
-  }
-  throw Error("scan: no kernel for this (dtype, op, acc)");
-}
-
 void launch_any(DType t, Op op, DType acc, DType out_t, const kern::ScanArgs& a, const Launch& l) {
-  switch (op) {
-    case Op::Sum: return launch_op<SumOp>(t, acc, out_t, a, l);
-    case Op::Min: return launch_op<MinOp>(t, acc, out_t, a, l);
-    case Op::Max: return launch_op<MaxOp>(t, acc, out_t, a, l);
-    default: break;
-  }
-  throw Error("scan: op must be SUM, MIN or MAX");
+  const bool found = visit_combo<PlainOps>(op, t, acc, [&](auto c) {
+    using C = decltype(c);
+    launch_out<typename C::op, typename C::elem, typename C::acc>(t, out_t, a, l);
+  });
+  if (!found) throw Error("scan: no kernel for this (dtype, op, acc)");
 }
 
 int vec_elems(DType t) { return static_cast<int>(16 / dtype_size(t)); }
@@ -486,9 +445,7 @@ ScanWorkspace::ScanWorkspace(int device, int64_t max_tiles) : max_tiles_(max_til
   int cus = 0;
   MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
   num_cus_ = cus > 0 ? cus : 256;
-  int prev = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-  MIREDUCE_HIP_THROW(hipSetDevice(device));
+  const DeviceGuard guard(device);
   const size_t desc_bytes = static_cast<size_t>(max_tiles) * 32;
   MIREDUCE_HIP_THROW(hipExtMallocWithFlags(reinterpret_cast<void**>(&desc_), desc_bytes, hipDeviceMallocUncached));
   MIREDUCE_HIP_THROW(hipMemset(desc_, 0, desc_bytes));
@@ -499,7 +456,6 @@ ScanWorkspace::ScanWorkspace(int device, int64_t max_tiles) : max_tiles_(max_til
   MIREDUCE_HIP_THROW(hipMalloc(reinterpret_cast<void**>(&ctrl_), 16));
   MIREDUCE_HIP_THROW(hipMemset(ctrl_, 0, 16));
   MIREDUCE_HIP_THROW(hipDeviceSynchronize());
-  MIREDUCE_HIP_THROW(hipSetDevice(prev));
 }
 
 ScanWorkspace::~ScanWorkspace() {
@@ -512,12 +468,8 @@ ScanWorkspace::~ScanWorkspace() {
 
 unsigned ScanWorkspace::error() const {
   unsigned v = 0;
-  int prev = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-  MIREDUCE_HIP_THROW(hipSetDevice(device_));
-  const hipError_t e = hipMemcpy(&v, state_ + 1, sizeof v, hipMemcpyDeviceToHost);
-  (void)hipSetDevice(prev);
-  MIREDUCE_HIP_THROW(e);
+  const DeviceGuard guard(device_);
+  MIREDUCE_HIP_THROW(hipMemcpy(&v, state_ + 1, sizeof v, hipMemcpyDeviceToHost));
   return v;
 }
 
@@ -539,13 +491,14 @@ ScanPlan plan_scan(const void* in, const void* out, size_t n, DType t, DType out
   MIREDUCE_REQUIRE(cfg.max_tiles_per_launch >= 0 && cfg.wg_per_cu >= 0 && cfg.max_blocks >= 0,
                    "scan: negative geometry");
   MIREDUCE_REQUIRE(cfg.debug_lookback_width >= 0 && cfg.debug_lookback_width <= 64, "scan: look-back width is 1..64");
-  const uint64_t pad = (reinterpret_cast<uintptr_t>(in) % 16) / es;
+  const kern::TileSpan sp = kern::tile_span(in, n, es);
+  const uint64_t pad = sp.pad;
   p.items_per_thread = static_cast<int>(N) * kScanVectors;
   p.tile_elems = N * kern::kScanTileVecs;
   p.single_pass = cfg.single_pass;
   p.head = n ? std::min<uint64_t>(n, pad ? N - pad : 0) : 0;
   p.tail = (n - p.head) % N;
-  p.tiles = n ? (pad + n + p.tile_elems - 1) / p.tile_elems : 0;
+  p.tiles = kern::tile_count(sp, p.tile_elems);
   p.vector_stores = (reinterpret_cast<uintptr_t>(out) - pad * os) % 16 == 0;
   uint64_t per = cfg.max_tiles_per_launch ? static_cast<uint64_t>(cfg.max_tiles_per_launch) : static_cast<uint64_t>(kScanMaxTiles);
   per = std::min<uint64_t>(per, static_cast<uint64_t>(ws_max_tiles));
@@ -575,12 +528,12 @@ ScanPlan scan(const void* in, size_t n, DType t, Op op, DType acc, DType out_t, 
                      "scan: out may be in (equal element sizes) but must not overlap it otherwise");
   }
   const ScanPlan p = plan_scan(in, out, n, t, out_t, cfg, ws.num_cus(), ws.max_tiles());
-  const uint64_t pad = (reinterpret_cast<uintptr_t>(in) % 16) / es;
+  const kern::TileSpan sp = kern::tile_span(in, n, es);
   kern::ScanArgs a{};
-  a.vin = static_cast<const char*>(in) - pad * es;
-  a.vout = static_cast<char*>(out) - pad * os;
-  a.pad = pad;
-  a.end = pad + n;
+  a.vin = sp.vin;
+  a.vout = static_cast<char*>(out) - sp.pad * os;
+  a.pad = sp.pad;
+  a.end = sp.end;
   a.partials = ws.partials();
   a.desc = ws.descriptors();
   a.state = ws.state();

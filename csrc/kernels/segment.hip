@@ -30,11 +30,14 @@
 #include <type_traits>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/segment.hpp"
 #include "mireduce/vec16.hpp"
 #include "reduce_kernels.hpp"
+#include "tile_load.hpp"
 
 namespace mireduce {
 namespace kern {
@@ -56,13 +59,6 @@ struct SegArgs {
   void* out;               // AccT[S]
   void* pieces;            // AccT slots: first_piece[tiles], then last_piece[tiles]
 };
-
-template <class T, class AccT>
-__device__ __forceinline__ T seg_to_elem(AccT v) {
-  if constexpr (std::is_same_v<T, AccT>) return v;
-  else if constexpr (is_half16_v<T>) return T::from_float(v);
-  else return static_cast<T>(v);
-}
 
 // The offsets of one tile: raw words from LDS (staged) or global memory; clamped on use.
 struct TileOffsets {
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(kScanBlock) void segment_tiles(SegArgs a) {
   __shared__ AccT s_red[kSegWaves];
   __shared__ unsigned s_rowflags;
   const AccT ident = OpT::template identity<AccT>();
-  const T ident_elem = seg_to_elem<T>(ident);
+  const T ident_elem = from_acc<T>(ident);
   AccT* const out = static_cast<AccT*>(a.out);
   AccT* const first = static_cast<AccT*>(a.pieces);
   AccT* const last = first + a.tiles;
@@ -317,40 +313,12 @@ void launch_typed(const kern::SegArgs& a, const Launch& l) {
   kern::segment_spans<OpT, AccT><<<l.span_grid, kern::kSpanBlock, 0, l.stream>>>(a, l.tile_elems);
 }
 
-template <class OpT>
-void launch_op(DType t, DType acc, const kern::SegArgs& a, const Launch& l) {
-  constexpr bool kFused = std::is_same_v<OpT, SumSqOp> || std::is_same_v<OpT, AbsMaxOp>;
-  constexpr bool kWidens = std::is_same_v<OpT, SumOp> || std::is_same_v<OpT, SumSqOp>;
-  switch (t) {
-    case DType::Int32:
-      if constexpr (!kFused) {
-        if (acc == DType::Int32) return launch_typed<OpT, int32_t, int32_t>(a, l);
-        if constexpr (kWidens) return launch_typed<OpT, int32_t, int64_t>(a, l);
-      }
-      break;
-    case DType::Int64:
-      if constexpr (!kFused) return launch_typed<OpT, int64_t, int64_t>(a, l);
-      break;
-    case DType::Float32:
-      if (acc == DType::Float32) return launch_typed<OpT, float, float>(a, l);
-      if constexpr (kWidens) return launch_typed<OpT, float, double>(a, l);
-      break;
-    case DType::Float64: return launch_typed<OpT, double, double>(a, l);
-    case DType::BFloat16: return launch_typed<OpT, bf16_t, float>(a, l);
-    case DType::Float16: return launch_typed<OpT, f16_t, float>(a, l);
-  }
-  throw Error("segment_reduce: no kernel for this (dtype, op, acc)");
-}
-
 void launch_any(DType t, Op op, DType acc, const kern::SegArgs& a, const Launch& l) {
-  switch (op) {
-    case Op::Sum: return launch_op<SumOp>(t, acc, a, l);
-    case Op::Min: return launch_op<MinOp>(t, acc, a, l);
-    case Op::Max: return launch_op<MaxOp>(t, acc, a, l);
-    case Op::SumSq: return launch_op<SumSqOp>(t, acc, a, l);
-    case Op::AbsMax: return launch_op<AbsMaxOp>(t, acc, a, l);
-  }
-  throw Error("segment_reduce: unknown op");
+  const bool found = visit_combo(op, t, acc, [&](auto c) {
+    using C = decltype(c);
+    launch_typed<typename C::op, typename C::elem, typename C::acc>(a, l);
+  });
+  if (!found) throw Error("segment_reduce: no kernel for this (dtype, op, acc)");
 }
 
 uint64_t tile_elems_of(DType t) { return kern::kSegTileVecs * (16 / dtype_size(t)); }
@@ -382,12 +350,8 @@ SegmentWorkspace::SegmentWorkspace(int device, int64_t max_tiles) : max_tiles_(m
   int cus = 0;
   MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
   num_cus_ = cus > 0 ? cus : 256;
-  int prev = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-  MIREDUCE_HIP_THROW(hipSetDevice(device));
-  const hipError_t e = hipMalloc(&pieces_, static_cast<size_t>(max_tiles) * 16);
-  (void)hipSetDevice(prev);
-  MIREDUCE_HIP_THROW(e);
+  const DeviceGuard guard(device);
+  MIREDUCE_HIP_THROW(hipMalloc(&pieces_, static_cast<size_t>(max_tiles) * 16));
 }
 
 SegmentWorkspace::~SegmentWorkspace() { (void)hipFree(pieces_); }
@@ -411,17 +375,17 @@ SegmentPlan segment_reduce(const void* in, uint64_t n, DType t, Op op, DType acc
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(in) % es == 0, "segment_reduce: x must be aligned to its element size");
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % dtype_size(acc) == 0,
                    "segment_reduce: offsets / out must be aligned to their element size");
-  const uint64_t pad = (reinterpret_cast<uintptr_t>(in) % 16) / es;
+  const kern::TileSpan sp = kern::tile_span(in, n, es);
   SegmentPlan p;
   p.tile_elems = tile_elems_of(t);
-  p.tiles = n ? (pad + n + p.tile_elems - 1) / p.tile_elems : 0;
+  p.tiles = kern::tile_count(sp, p.tile_elems);
   grids(p.tiles, segments, cfg, ws.num_cus(), &p);
   if (segments == 0) return p;
   MIREDUCE_REQUIRE(p.tiles <= static_cast<uint64_t>(ws.max_tiles()), "segment_reduce: the workspace is too small for this input");
   kern::SegArgs a{};
-  a.vin = static_cast<const char*>(in) - pad * es;
-  a.pad = pad;
-  a.end = pad + n;
+  a.vin = sp.vin;
+  a.pad = sp.pad;
+  a.end = sp.end;
   a.n = n;
   a.offsets = offsets;
   a.S = static_cast<int64_t>(segments);

@@ -15,6 +15,7 @@
 #include "mireduce/arg_reduce.hpp"
 #include "mireduce/check.hpp"
 #include "mireduce/cpu_reference.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/direct.hpp"
 #include "mireduce/final_line.hpp"
 #include "mireduce/histogram.hpp"
@@ -154,12 +155,9 @@ PYBIND11_MODULE(_C, m) {
   });
 
   m.def("mem_info", [](int dev) {
-    int prev = 0;
-    check_hip(hipGetDevice(&prev), "hipGetDevice");
-    check_hip(hipSetDevice(dev), "hipSetDevice");
+    const DeviceGuard guard(dev);
     size_t free_b = 0, total_b = 0;
     check_hip(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    check_hip(hipSetDevice(prev), "hipSetDevice");
     return py::make_tuple(free_b, total_b);
   });
 

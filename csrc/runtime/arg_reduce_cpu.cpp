@@ -10,6 +10,7 @@
 
 #include "mireduce/arg_reduce.hpp"
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 
 namespace mireduce {
@@ -91,14 +92,10 @@ void arg_rows(const T* in, size_t rows, size_t cols, T* out_value, int64_t* out_
 
 template <bool MAX>
 void arg_dispatch(const void* in, size_t rows, size_t cols, DType t, void* ov, int64_t* oi) {
-  switch (t) {
-    case DType::Int32: arg_rows<MAX>(static_cast<const int32_t*>(in), rows, cols, static_cast<int32_t*>(ov), oi); break;
-    case DType::Int64: arg_rows<MAX>(static_cast<const int64_t*>(in), rows, cols, static_cast<int64_t*>(ov), oi); break;
-    case DType::Float32: arg_rows<MAX>(static_cast<const float*>(in), rows, cols, static_cast<float*>(ov), oi); break;
-    case DType::Float64: arg_rows<MAX>(static_cast<const double*>(in), rows, cols, static_cast<double*>(ov), oi); break;
-    case DType::BFloat16: arg_rows<MAX>(static_cast<const bf16_t*>(in), rows, cols, static_cast<bf16_t*>(ov), oi); break;
-    case DType::Float16: arg_rows<MAX>(static_cast<const f16_t*>(in), rows, cols, static_cast<f16_t*>(ov), oi); break;
-  }
+  visit_dtype(t, [&](auto z) {
+    using T = decltype(z);
+    arg_rows<MAX>(static_cast<const T*>(in), rows, cols, static_cast<T*>(ov), oi);
+  });
 }
 
 }  // namespace

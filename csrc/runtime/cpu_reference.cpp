@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 
@@ -103,14 +104,7 @@ void dispatch_acc(const void* in, size_t n, DType acc, void* out, int threads) {
 
 template <class OpT>
 void dispatch_t(const void* in, size_t n, DType t, DType acc, void* out, int threads) {
-  switch (t) {
-    case DType::Int32: dispatch_acc<OpT, int32_t>(in, n, acc, out, threads); break;
-    case DType::Int64: dispatch_acc<OpT, int64_t>(in, n, acc, out, threads); break;
-    case DType::Float32: dispatch_acc<OpT, float>(in, n, acc, out, threads); break;
-    case DType::Float64: dispatch_acc<OpT, double>(in, n, acc, out, threads); break;
-    case DType::BFloat16: dispatch_acc<OpT, bf16_t>(in, n, acc, out, threads); break;
-    case DType::Float16: dispatch_acc<OpT, f16_t>(in, n, acc, out, threads); break;
-  }
+  visit_dtype(t, [&](auto z) { dispatch_acc<OpT, decltype(z)>(in, n, acc, out, threads); });
 }
 
 }  // namespace
@@ -152,15 +146,9 @@ double abs_sum_t(const void* in, size_t n, int threads) {
 }  // namespace
 
 double cpu_abs_sum(const void* in, size_t n, DType t, int threads) {
-  switch (t) {
-    case DType::Int32: return abs_sum_t<int32_t>(in, n, threads);
-    case DType::Int64: return abs_sum_t<int64_t>(in, n, threads);
-    case DType::Float32: return abs_sum_t<float>(in, n, threads);
-    case DType::Float64: return abs_sum_t<double>(in, n, threads);
-    case DType::BFloat16: return abs_sum_t<bf16_t>(in, n, threads);
-    case DType::Float16: return abs_sum_t<f16_t>(in, n, threads);
-  }
-  return 0.0;
+  double r = 0.0;
+  visit_dtype(t, [&](auto z) { r = abs_sum_t<decltype(z)>(in, n, threads); });
+  return r;
 }
 
 void cpu_fold(const void* partials, size_t count, DType acc, Op op, void* out) {

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/histogram.hpp"
 
@@ -73,15 +74,10 @@ void cpu_histogram(const void* in, uint64_t n, DType t, int64_t bins, double lo,
     std::fill(out, out + bins, int64_t{0});
     *dropped = 0;
   }
-  switch (t) {
-    case DType::Int32: return count_typed(static_cast<const int32_t*>(in), n, bins, lo, hi, out, dropped);
-    case DType::Int64: return count_typed(static_cast<const int64_t*>(in), n, bins, lo, hi, out, dropped);
-    case DType::Float32: return count_typed(static_cast<const float*>(in), n, bins, lo, hi, out, dropped);
-    case DType::Float64: return count_typed(static_cast<const double*>(in), n, bins, lo, hi, out, dropped);
-    case DType::BFloat16: return count_typed(static_cast<const bf16_t*>(in), n, bins, lo, hi, out, dropped);
-    case DType::Float16: return count_typed(static_cast<const f16_t*>(in), n, bins, lo, hi, out, dropped);
-  }
-  throw Error("histogram: unknown dtype");
+  const bool found = visit_dtype(t, [&](auto z) {
+    count_typed(static_cast<const decltype(z)*>(in), n, bins, lo, hi, out, dropped);
+  });
+  if (!found) throw Error("histogram: unknown dtype");
 }
 
 }  // namespace mireduce

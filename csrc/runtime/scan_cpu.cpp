@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/scan.hpp"
@@ -11,14 +12,6 @@
 namespace mireduce {
 
 namespace {
-
-template <class OutT, class A>
-OutT to_out(A v) {
-  if constexpr (std::is_same_v<OutT, A>) return v;
-  else if constexpr (is_half16_v<OutT>) return OutT::from_float(v);
-  else if constexpr (std::is_integral_v<OutT>) return static_cast<OutT>(static_cast<std::make_unsigned_t<A>>(v));
-  else return static_cast<OutT>(v);
-}
 
 // The running value: Neumaier-compensated fp64 for floating sums (as cpu_reference.cpp), else the
 // accumulator itself combined with the functor.
@@ -49,9 +42,9 @@ void scan_typed(const T* in, size_t n, OutT* out, bool exclusive, const A* carry
   Running<OpT, A> run(carry_in ? *carry_in : OpT::template identity<A>());
   for (size_t i = 0; i < n; ++i) {
     const A x = static_cast<A>(in[i]);  // read before the store: out may be in
-    if (exclusive) out[i] = to_out<OutT>(run.value());
+    if (exclusive) out[i] = from_acc<OutT>(run.value());
     run.add(x);
-    if (!exclusive) out[i] = to_out<OutT>(run.value());
+    if (!exclusive) out[i] = from_acc<OutT>(run.value());
   }
   if (carry_out) *carry_out = run.value();
 }
@@ -65,22 +58,6 @@ void scan_out(DType t, DType out_t, const void* in, size_t n, void* out, bool ex
     if (out_t == t) return scan_typed<OpT, T, A, T>(i, n, static_cast<T*>(out), exclusive, c0, c1);
   }
   scan_typed<OpT, T, A, A>(i, n, static_cast<A*>(out), exclusive, c0, c1);
-}
-
-template <class OpT>
-void scan_op(DType t, DType acc, DType out_t, const void* in, size_t n, void* out, bool ex, const void* ci, void* co) {
-  switch (t) {
-    case DType::Int32:
-      if (acc == DType::Int32) return scan_out<OpT, int32_t, int32_t>(t, out_t, in, n, out, ex, ci, co);
-      return scan_out<OpT, int32_t, int64_t>(t, out_t, in, n, out, ex, ci, co);
-    case DType::Int64: return scan_out<OpT, int64_t, int64_t>(t, out_t, in, n, out, ex, ci, co);
-    case DType::Float32:
-      if (acc == DType::Float32) return scan_out<OpT, float, float>(t, out_t, in, n, out, ex, ci, co);
-      return scan_out<OpT, float, double>(t, out_t, in, n, out, ex, ci, co);
-    case DType::Float64: return scan_out<OpT, double, double>(t, out_t, in, n, out, ex, ci, co);
-    case DType::BFloat16: return scan_out<OpT, bf16_t, float>(t, out_t, in, n, out, ex, ci, co);
-    case DType::Float16: return scan_out<OpT, f16_t, float>(t, out_t, in, n, out, ex, ci, co);
-  }
 }
 
 }  // namespace
@@ -99,11 +76,10 @@ void cpu_scan(const void* in, size_t n, DType t, Op op, DType acc, DType out_t, 
     MIREDUCE_REQUIRE(!overlap || (i0 == o0 && es == os),
                      "scan: out may be in (equal element sizes) but must not overlap it otherwise");
   }
-  switch (op) {
-    case Op::Sum: return scan_op<SumOp>(t, acc, out_t, in, n, out, exclusive, carry_in, carry_out);
-    case Op::Min: return scan_op<MinOp>(t, acc, out_t, in, n, out, exclusive, carry_in, carry_out);
-    default: return scan_op<MaxOp>(t, acc, out_t, in, n, out, exclusive, carry_in, carry_out);
-  }
+  visit_combo<PlainOps>(op, t, acc, [&](auto c) {  // found: acc_supported() above
+    using C = decltype(c);
+    scan_out<typename C::op, typename C::elem, typename C::acc>(t, out_t, in, n, out, exclusive, carry_in, carry_out);
+  });
 }
 
 }  // namespace mireduce

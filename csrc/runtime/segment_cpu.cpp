@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "mireduce/check.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/segment.hpp"
@@ -37,30 +38,6 @@ void segments_typed(const T* in, const int64_t* off, uint64_t S, A* out) {
   }
 }
 
-template <class OpT>
-void segments_op(DType t, DType acc, const void* in, const int64_t* off, uint64_t S, void* out) {
-  constexpr bool kFused = std::is_same_v<OpT, SumSqOp> || std::is_same_v<OpT, AbsMaxOp>;
-  switch (t) {
-    case DType::Int32:
-      if constexpr (!kFused) {
-        if (acc == DType::Int32)
-          return segments_typed<OpT>(static_cast<const int32_t*>(in), off, S, static_cast<int32_t*>(out));
-        return segments_typed<OpT>(static_cast<const int32_t*>(in), off, S, static_cast<int64_t*>(out));
-      }
-      break;
-    case DType::Int64:
-      if constexpr (!kFused) return segments_typed<OpT>(static_cast<const int64_t*>(in), off, S, static_cast<int64_t*>(out));
-      break;
-    case DType::Float32:
-      if (acc == DType::Float32) return segments_typed<OpT>(static_cast<const float*>(in), off, S, static_cast<float*>(out));
-      return segments_typed<OpT>(static_cast<const float*>(in), off, S, static_cast<double*>(out));
-    case DType::Float64: return segments_typed<OpT>(static_cast<const double*>(in), off, S, static_cast<double*>(out));
-    case DType::BFloat16: return segments_typed<OpT>(static_cast<const bf16_t*>(in), off, S, static_cast<float*>(out));
-    case DType::Float16: return segments_typed<OpT>(static_cast<const f16_t*>(in), off, S, static_cast<float*>(out));
-  }
-  throw Error("segment_reduce: no host reference for this (dtype, op, acc)");
-}
-
 }  // namespace
 
 int64_t segment_first_bad_offset(const int64_t* offsets, uint64_t segments, uint64_t n) {
@@ -87,14 +64,12 @@ void cpu_segment_reduce(const void* in, uint64_t n, DType t, Op op, DType acc, c
                   std::to_string(offsets[bad - 1]));
     throw Error("segment_reduce: " + at + " must be the number of elements " + std::to_string(n));
   }
-  switch (op) {
-    case Op::Sum: return segments_op<SumOp>(t, acc, in, offsets, segments, out);
-    case Op::Min: return segments_op<MinOp>(t, acc, in, offsets, segments, out);
-    case Op::Max: return segments_op<MaxOp>(t, acc, in, offsets, segments, out);
-    case Op::SumSq: return segments_op<SumSqOp>(t, acc, in, offsets, segments, out);
-    case Op::AbsMax: return segments_op<AbsMaxOp>(t, acc, in, offsets, segments, out);
-  }
-  throw Error("segment_reduce: unknown op");
+  const bool found = visit_combo(op, t, acc, [&](auto c) {
+    using C = decltype(c);
+    segments_typed<typename C::op>(static_cast<const typename C::elem*>(in), offsets, segments,
+                                   static_cast<typename C::acc*>(out));
+  });
+  if (!found) throw Error("segment_reduce: no host reference for this (dtype, op, acc)");
 }
 
 }  // namespace mireduce

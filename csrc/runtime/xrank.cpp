@@ -8,19 +8,11 @@
 #include <cstring>
 
 #include "mireduce/check.hpp"
+#include "mireduce/device.hpp"
 
 namespace mireduce {
 
 namespace {
-struct DeviceGuard {
-  int prev = 0;
-  explicit DeviceGuard(int dev) {
-    MIREDUCE_HIP_THROW(hipGetDevice(&prev));
-    MIREDUCE_HIP_THROW(hipSetDevice(dev));
-  }
-  ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
 constexpr size_t kMailboxBytes = 4096;  // one page: IPC maps whole allocations
 }  // namespace
 

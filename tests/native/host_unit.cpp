@@ -5,9 +5,11 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mireduce/cli.hpp"
+#include "mireduce/combo.hpp"
 #include "mireduce/fault.hpp"
 #include "mireduce/mt19937.hpp"
 #include "mireduce/peer_access.hpp"
@@ -185,7 +187,75 @@ static void test_peer_verdict() {
   CHECK(f.no_peer(1) && !f.no_peer(0) && !f.at(1, 0, "unit"));
 }
 
+// combo.hpp's list against types.hpp's predicates, and the numbering that tuning JSON and the
+// flat kernel's dispatch table are keyed by.
+static int combo_index_before_the_list(Op op, DType t, DType acc) {
+  constexpr DType I32 = DType::Int32, I64 = DType::Int64, F32 = DType::Float32, F64 = DType::Float64,
+                  BF16 = DType::BFloat16, F16 = DType::Float16;
+  static const struct { Op op; DType t, acc; } numbered[29] = {
+      {Op::Sum, I32, I64},      {Op::Sum, I32, I32},     {Op::Min, I32, I32},      {Op::Max, I32, I32},      // 0..3
+      {Op::Sum, I64, I64},      {Op::Min, I64, I64},     {Op::Max, I64, I64},                                // 4..6
+      {Op::Sum, F32, F64},      {Op::Sum, F32, F32},     {Op::Min, F32, F32},      {Op::Max, F32, F32},      // 7..10
+      {Op::Sum, F64, F64},      {Op::Min, F64, F64},     {Op::Max, F64, F64},                                // 11..13
+      {Op::Sum, BF16, F32},     {Op::Min, BF16, F32},    {Op::Max, BF16, F32},                               // 14..16
+      {Op::Sum, F16, F32},      {Op::Min, F16, F32},     {Op::Max, F16, F32},                                // 17..19
+      {Op::SumSq, F32, F64},    {Op::SumSq, F32, F32},   {Op::SumSq, F64, F64},                              // 20..22
+      {Op::SumSq, BF16, F32},   {Op::SumSq, F16, F32},                                                       // 23..24
+      {Op::AbsMax, F32, F32},   {Op::AbsMax, F64, F64},  {Op::AbsMax, BF16, F32},  {Op::AbsMax, F16, F32}};  // 25..28
+  for (int i = 0; i < 29; ++i)
+    if (numbered[i].op == op && numbered[i].t == t && numbered[i].acc == acc) return i;
+  return -1;
+}
+
+static void test_combos() {
+  const Op ops[] = {Op::Sum, Op::Min, Op::Max, Op::SumSq, Op::AbsMax};
+  const DType types[] = {DType::Int32, DType::Int64, DType::Float32, DType::Float64, DType::BFloat16, DType::Float16};
+  CHECK(kCombos == 29);
+  int supported = 0;
+  bool seen[kCombos] = {};
+  for (DType t : types)
+    for (Op op : ops) {
+      bool any = false;
+      for (DType acc : types) {
+        int visits = 0;
+        const bool found = visit_combo(op, t, acc, [&](auto c) {
+          using C = decltype(c);
+          ++visits;
+          CHECK(sizeof(typename C::elem) == dtype_size(t) && dtype_of<typename C::elem>::value == t);
+          CHECK(sizeof(typename C::acc) == dtype_size(acc) && dtype_of<typename C::acc>::value == acc);
+          CHECK(op_of<typename C::op>::value == op);
+          CHECK((std::is_same_v<typename C::op, SumOp>) == (op == Op::Sum));
+          CHECK((std::is_same_v<typename C::op, MinOp>) == (op == Op::Min));
+          CHECK((std::is_same_v<typename C::op, MaxOp>) == (op == Op::Max));
+          CHECK((std::is_same_v<typename C::op, SumSqOp>) == (op == Op::SumSq));
+          CHECK((std::is_same_v<typename C::op, AbsMaxOp>) == (op == Op::AbsMax));
+        });
+        CHECK(found == acc_supported(t, op, acc));
+        CHECK(visits == (found ? 1 : 0));
+        const int i = combo_index(op, t, acc);
+        CHECK(i == combo_index_before_the_list(op, t, acc));
+        CHECK(found == (i >= 0));
+        if (i >= 0 && i < kCombos) {
+          CHECK(!seen[i]);
+          seen[i] = true;
+        }
+        supported += found ? 1 : 0;
+        any = any || found;
+        // the operator subset: the fused operators are not found, the others as before
+        const bool plain = visit_combo<PlainOps>(op, t, acc, [](auto) {});
+        CHECK(plain == (found && !op_is_fused(op)));
+      }
+      if (any) CHECK(combo_index(op, t, default_acc(t, op)) >= 0);
+    }
+  CHECK(supported == 29);
+  for (bool s : seen) CHECK(s);
+  int visited = 0;
+  CHECK(visit_dtype(DType::BFloat16, [&](auto z) { visited += std::is_same_v<decltype(z), bf16_t> ? 1 : 0; }));
+  CHECK(visited == 1 && !visit_dtype(static_cast<DType>(99), [](auto) {}));
+}
+
 int main() {
+  test_combos();
   test_peer_verdict();
   test_cli();
   test_peer_plan();
