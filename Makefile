@@ -166,7 +166,7 @@ $(BUILD)/bin/cpp_consumer: examples/cpp_consumer/main.cpp $(SHLIB) $(HEADERS)
 	$(HOSTCXX) $(HOSTFLAGS) $< $(LINK_BIN) $(LDLIBS) -o $@
 
 # Native unit tests (host code only) and the bootstrap multi-process test.
-UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/segment_unit $(BUILD)/bin/histogram_unit $(BUILD)/bin/bootstrap_test
+UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/segment_unit $(BUILD)/bin/histogram_unit $(BUILD)/bin/sort_unit $(BUILD)/bin/bootstrap_test
 unit: $(UNIT)
 
 UNIT_SRCS := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
@@ -196,6 +196,13 @@ $(BUILD)/bin/histogram_unit: $(HISTOGRAM_UNIT_SRCS) $(HEADERS)
 	@mkdir -p $(dir $@)
 	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(HISTOGRAM_UNIT_SRCS) -o $@
 
+# The radix keys at every edge, cpu_sort / cpu_group_by_key against a naive stable insertion sort and the
+# planner's invariants (tests/native/sort_unit.cpp; host code only).
+SORT_UNIT_SRCS := tests/native/sort_unit.cpp csrc/runtime/sort_cpu.cpp csrc/runtime/histogram_cpu.cpp
+$(BUILD)/bin/sort_unit: $(SORT_UNIT_SRCS) $(HEADERS)
+	@mkdir -p $(dir $@)
+	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SORT_UNIT_SRCS) -o $@
+
 $(BUILD)/bin/bootstrap_test: tests/native/bootstrap_test.cpp $(COMMLIB) $(SHLIB) $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(HOSTCXX) $(HOSTFLAGS) $< -Wl,--whole-archive $(COMMLIB) -Wl,--no-whole-archive $(LINK_BIN) \
@@ -215,6 +222,8 @@ asan: csrc/apps/reduce_mpi.cpp
 	    $(SEGMENT_UNIT_SRCS) -o $(BUILD)/asan/segment_unit
 	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
 	    $(HISTOGRAM_UNIT_SRCS) -o $(BUILD)/asan/histogram_unit
+	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
+	    $(SORT_UNIT_SRCS) -o $(BUILD)/asan/sort_unit
 
 # Race detection: the threaded host reference reducers / arg-reductions under
 # ThreadSanitizer (tests/native/race_unit.cpp; exits non-zero on any report).

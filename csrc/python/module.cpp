@@ -27,6 +27,7 @@
 #include "mireduce/reduce_many.hpp"
 #include "mireduce/scan.hpp"
 #include "mireduce/segment.hpp"
+#include "mireduce/sort.hpp"
 #include "mireduce/trace.hpp"
 #include "mireduce/types.hpp"
 #include "mireduce/version.hpp"
@@ -746,6 +747,99 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("bins"), py::arg("lo"), py::arg("hi"),
       py::arg("out_ptr"), py::arg("dropped_ptr"), py::arg("accumulate") = false);
+  // Radix sort (csrc/kernels/sort.hip, csrc/runtime/sort_cpu.cpp).
+  auto sort_plan_dict = [](const SortPlan& p) {
+    py::dict d;
+    d["key_bytes"] = p.key_bytes;
+    d["key_bits"] = p.key_bits;
+    d["radix_bits"] = p.radix_bits;
+    d["passes"] = p.passes;
+    d["block"] = p.block;
+    d["grid"] = p.grid;
+    d["tile_elems"] = p.tile_elems;
+    d["tiles"] = p.tiles;
+    d["tiles_per_wg"] = p.tiles_per_wg;
+    d["lds_bytes"] = p.lds_bytes;
+    d["temp_bytes"] = p.temp_bytes;
+    return d;
+  };
+  auto sort_cfg = [](int max_blocks, int wg_per_cu, int radix_bits) {
+    SortConfig cfg;
+    cfg.max_blocks = max_blocks;
+    cfg.wg_per_cu = wg_per_cu;
+    cfg.radix_bits = radix_bits;
+    return cfg;
+  };
+  m.def(
+      "sort",
+      [sort_plan_dict, sort_cfg](uintptr_t in, uint64_t n, int dtype, bool descending, uintptr_t out_keys, uintptr_t out_idx,
+                                 uintptr_t temp, uint64_t temp_bytes, uintptr_t stream, int max_blocks, int wg_per_cu,
+                                 int radix_bits) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return sort_plan_dict(sort(as_ptr<const void>(in), n, static_cast<DType>(dtype), descending, as_ptr<void>(out_keys),
+                                   as_ptr<int64_t>(out_idx), as_ptr<void>(temp), temp_bytes, as_stream(stream),
+                                   sort_cfg(max_blocks, wg_per_cu, radix_bits)));
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("descending"), py::arg("out_keys_ptr"),
+      py::arg("out_idx_ptr"), py::arg("temp_ptr"), py::arg("temp_bytes"), py::arg("stream") = 0, py::arg("max_blocks") = 0,
+      py::arg("wg_per_cu") = 0, py::arg("radix_bits") = 0);
+  m.def(
+      "group_by_key",
+      [sort_plan_dict, sort_cfg](uintptr_t ids, uint64_t n, int dtype, int64_t bins, uintptr_t order, uintptr_t counts,
+                                 uintptr_t dropped, uintptr_t temp, uint64_t temp_bytes, uintptr_t stream, int max_blocks,
+                                 int wg_per_cu, int radix_bits) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return sort_plan_dict(group_by_key(as_ptr<const void>(ids), n, static_cast<DType>(dtype), bins, as_ptr<int64_t>(order),
+                                           as_ptr<int64_t>(counts), as_ptr<int64_t>(dropped), as_ptr<void>(temp), temp_bytes,
+                                           as_stream(stream), sort_cfg(max_blocks, wg_per_cu, radix_bits)));
+      },
+      py::arg("ids_ptr"), py::arg("n"), py::arg("dtype"), py::arg("bins"), py::arg("order_ptr"), py::arg("counts_ptr"),
+      py::arg("dropped_ptr"), py::arg("temp_ptr"), py::arg("temp_bytes"), py::arg("stream") = 0, py::arg("max_blocks") = 0,
+      py::arg("wg_per_cu") = 0, py::arg("radix_bits") = 0);
+  m.def(
+      "cpu_sort",
+      [](uintptr_t in, uint64_t n, int dtype, bool descending, uintptr_t out_keys, uintptr_t out_idx) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        py::gil_scoped_release nogil;
+        cpu_sort(as_ptr<const void>(in), n, static_cast<DType>(dtype), descending, as_ptr<void>(out_keys),
+                 as_ptr<int64_t>(out_idx));
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("descending"), py::arg("out_keys_ptr"),
+      py::arg("out_idx_ptr"));
+  m.def(
+      "cpu_group_by_key",
+      [](uintptr_t ids, uint64_t n, int dtype, int64_t bins, uintptr_t order, uintptr_t counts, uintptr_t dropped) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        py::gil_scoped_release nogil;
+        cpu_group_by_key(as_ptr<const void>(ids), n, static_cast<DType>(dtype), bins, as_ptr<int64_t>(order),
+                         as_ptr<int64_t>(counts), as_ptr<int64_t>(dropped));
+      },
+      py::arg("ids_ptr"), py::arg("n"), py::arg("dtype"), py::arg("bins"), py::arg("order_ptr"), py::arg("counts_ptr"),
+      py::arg("dropped_ptr"));
+  m.def(
+      "sort_plan",
+      [sort_plan_dict, sort_cfg](uint64_t n, int dtype, bool with_indices, int num_cus, int key_bits, int max_blocks,
+                                 int wg_per_cu, int radix_bits) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return sort_plan_dict(plan_sort(n, static_cast<DType>(dtype), with_indices, sort_cfg(max_blocks, wg_per_cu, radix_bits),
+                                        num_cus, key_bits));
+      },
+      py::arg("n"), py::arg("dtype"), py::arg("with_indices") = true, py::arg("num_cus") = 256, py::arg("key_bits") = 0,
+      py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0, py::arg("radix_bits") = 0);
+  m.def(
+      "sort_temp_bytes",
+      [](uint64_t n, int dtype, bool with_indices, bool group) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return sort_temp_bytes(n, static_cast<DType>(dtype), with_indices, group);
+      },
+      py::arg("n"), py::arg("dtype"), py::arg("with_indices") = true, py::arg("group") = false);
+  m.def(
+      "sort_check_args",
+      [](uint64_t n, int dtype) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        sort_check_args(n, static_cast<DType>(dtype));
+      },
+      py::arg("n"), py::arg("dtype"));
   m.def(
       "moments",
       [](uintptr_t in, uint64_t n, int dtype, uintptr_t out5, uintptr_t partials, int max_grid, int num_cus,
