@@ -22,6 +22,8 @@ struct ArgPlan {
   uint64_t splits = 1;       // long rows: workgroups per row (> 1: per-row tickets, the last one folds)
   int unroll = 0;            // 16-byte vectors in flight per lane (long rows) / row batches (short)
   int wg_per_cu = 0;         // resident workgroups per CU the grid was sized for
+  int variant = -1;          // kernel that ran: 0 long rows; 1, 2, 4 scalar short rows; 11, 12, 14 vector
+                             // short rows; 20 a wave per row (-1: nothing launched)
 };
 
 // Long-row tunables (0 = the gfx950 default; tools/arg_reduce_bw.py --sweep measures them).

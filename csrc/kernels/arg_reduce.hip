@@ -183,9 +183,14 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
     const V* vp = reinterpret_cast<const V*>(p + head);
     K bv = C::identity();
     int64_t bi = kNoIndex;
+    // Head and tail register an element only if it strictly beats the identity, as the vector
+    // slots do: a row whose elements all equal the identity registers none and answers index 0.
     if (s == 0 && static_cast<uint64_t>(tid) < head) {
-      bv = load_key<T, K>(p + tid);
-      bi = tid;
+      const K x = load_key<T, K>(p + tid);
+      if (C::beats(x, bv)) {
+        bv = x;
+        bi = tid;
+      }
     }
     K best[P][N];
     uint32_t trip[P][N];  // q = m * U + u: the u-th vector of this workgroup's m-th tile
@@ -252,7 +257,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
     if (s == S - 1 && static_cast<uint64_t>(tid) < a.cols - tb) {
       const K x = load_key<T, K>(p + tb + tid);
       const int64_t idx = static_cast<int64_t>(tb + tid);
-      if (C::pair_beats(x, idx, bv, bi)) {
+      if (C::beats(x, bv)) {  // strict: the tail lies behind every index this lane holds
         bv = x;
         bi = idx;
       }
@@ -322,9 +327,12 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
     const V* vp = reinterpret_cast<const V*>(p + head);
     K bv = C::identity();
     int64_t bi = kNoIndex;
-    if (static_cast<uint64_t>(lane) < head) {
-      bv = load_key<T, K>(p + lane);
-      bi = lane;
+    if (static_cast<uint64_t>(lane) < head) {  // strictly beats the identity, or stays unregistered
+      const K x = load_key<T, K>(p + lane);
+      if (C::beats(x, bv)) {
+        bv = x;
+        bi = lane;
+      }
     }
     K best[P][N];
     uint32_t trip[P][N];  // q = tile * U + u: vector q * 64 + lane
@@ -388,7 +396,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
     if (static_cast<uint64_t>(lane) < a.cols - tb) {
       const K x = load_key<T, K>(p + tb + lane);
       const int64_t idx = static_cast<int64_t>(tb + lane);
-      if (C::pair_beats(x, idx, bv, bi)) {
+      if (C::beats(x, bv)) {  // strict: the tail lies behind every index this lane holds
         bv = x;
         bi = idx;
       }
@@ -764,6 +772,7 @@ ArgPlan arg_reduce_rows(const void* in, size_t rows, size_t cols, DType t, Op op
   plan.splits = L.splits;
   plan.unroll = variant == kLong || variant == kWave ? unroll : kern::kArgUnroll;
   plan.wg_per_cu = resident;
+  plan.variant = variant;
   return plan;
 }
 

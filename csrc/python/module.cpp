@@ -514,6 +514,7 @@ PYBIND11_MODULE(_C, m) {
         d["splits"] = p.splits;
         d["unroll"] = p.unroll;
         d["wg_per_cu"] = p.wg_per_cu;
+        d["variant"] = p.variant;
         return d;
       },
       py::arg("in_ptr"), py::arg("rows"), py::arg("cols"), py::arg("dtype"), py::arg("op"), py::arg("out_value_ptr"),
