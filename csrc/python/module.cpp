@@ -28,6 +28,7 @@
 #include "mireduce/scan.hpp"
 #include "mireduce/segment.hpp"
 #include "mireduce/sort.hpp"
+#include "mireduce/topk.hpp"
 #include "mireduce/trace.hpp"
 #include "mireduce/types.hpp"
 #include "mireduce/version.hpp"
@@ -841,6 +842,79 @@ PYBIND11_MODULE(_C, m) {
         sort_check_args(n, static_cast<DType>(dtype));
       },
       py::arg("n"), py::arg("dtype"));
+  // Top-k selection (csrc/kernels/topk.hip, csrc/runtime/topk_cpu.cpp).
+  auto topk_plan_dict = [](const TopkPlan& p) {
+    py::dict d;
+    d["variant"] = p.variant;
+    d["grid"] = p.grid;
+    d["block"] = p.block;
+    d["lanes_per_row"] = p.lanes_per_row;
+    d["rows_per_wg"] = p.rows_per_wg;
+    d["items_per_lane"] = p.items_per_lane;
+    d["splits"] = p.splits;
+    d["chunk_elems"] = p.chunk_elems;
+    d["tile_elems"] = p.tile_elems;
+    d["key_bytes"] = p.key_bytes;
+    d["passes"] = p.passes;
+    d["launches"] = p.launches;
+    d["lds_bytes"] = p.lds_bytes;
+    d["temp_bytes"] = p.temp_bytes;
+    d["wave_max_cols"] = p.wave_max_cols;
+    d["wave_max_k"] = p.wave_max_k;
+    d["max_k"] = kTopkMaxK;
+    return d;
+  };
+  auto topk_cfg = [](int variant, int splits, int max_blocks, int wg_per_cu, int lanes_per_row) {
+    TopkConfig cfg;
+    cfg.variant = variant;
+    cfg.splits = splits;
+    cfg.max_blocks = max_blocks;
+    cfg.wg_per_cu = wg_per_cu;
+    cfg.lanes_per_row = lanes_per_row;
+    return cfg;
+  };
+  m.def(
+      "topk",
+      [topk_plan_dict, topk_cfg](uintptr_t in, uint64_t rows, uint64_t cols, int64_t k, int dtype, bool largest,
+                                 uintptr_t out_values, uintptr_t out_idx, uintptr_t temp, uint64_t temp_bytes, uintptr_t stream,
+                                 int variant, int splits, int max_blocks, int wg_per_cu, int lanes_per_row) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return topk_plan_dict(topk(as_ptr<const void>(in), rows, cols, k, static_cast<DType>(dtype), largest,
+                                   as_ptr<void>(out_values), as_ptr<int64_t>(out_idx), as_ptr<void>(temp), temp_bytes,
+                                   as_stream(stream), topk_cfg(variant, splits, max_blocks, wg_per_cu, lanes_per_row)));
+      },
+      py::arg("in_ptr"), py::arg("rows"), py::arg("cols"), py::arg("k"), py::arg("dtype"), py::arg("largest"),
+      py::arg("out_values_ptr"), py::arg("out_idx_ptr"), py::arg("temp_ptr"), py::arg("temp_bytes"), py::arg("stream") = 0,
+      py::arg("variant") = 0, py::arg("splits") = 0, py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0,
+      py::arg("lanes_per_row") = 0);
+  m.def(
+      "cpu_topk",
+      [](uintptr_t in, uint64_t rows, uint64_t cols, int64_t k, int dtype, bool largest, uintptr_t out_values,
+         uintptr_t out_idx) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        py::gil_scoped_release nogil;
+        cpu_topk(as_ptr<const void>(in), rows, cols, k, static_cast<DType>(dtype), largest, as_ptr<void>(out_values),
+                 as_ptr<int64_t>(out_idx));
+      },
+      py::arg("in_ptr"), py::arg("rows"), py::arg("cols"), py::arg("k"), py::arg("dtype"), py::arg("largest"),
+      py::arg("out_values_ptr"), py::arg("out_idx_ptr"));
+  m.def(
+      "topk_plan",
+      [topk_plan_dict, topk_cfg](uint64_t rows, uint64_t cols, int64_t k, int dtype, int num_cus, int variant, int splits,
+                                 int max_blocks, int wg_per_cu, int lanes_per_row) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return topk_plan_dict(plan_topk(rows, cols, k, static_cast<DType>(dtype), topk_cfg(variant, splits, max_blocks, wg_per_cu, lanes_per_row),
+                                        num_cus));
+      },
+      py::arg("rows"), py::arg("cols"), py::arg("k"), py::arg("dtype"), py::arg("num_cus") = 256, py::arg("variant") = 0,
+      py::arg("splits") = 0, py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0, py::arg("lanes_per_row") = 0);
+  m.def(
+      "topk_temp_bytes",
+      [](uint64_t rows, uint64_t cols, int64_t k, int dtype) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return topk_temp_bytes(rows, cols, k, static_cast<DType>(dtype));
+      },
+      py::arg("rows"), py::arg("cols"), py::arg("k"), py::arg("dtype"));
   m.def(
       "moments",
       [](uintptr_t in, uint64_t n, int dtype, uintptr_t out5, uintptr_t partials, int max_grid, int num_cus,

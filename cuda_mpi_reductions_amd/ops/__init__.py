@@ -13,3 +13,4 @@ from .scan import ScanConfig, cummax, cummin, cumsum, scan, scan_plan, scan_work
 from .segment import SegmentConfig, segment_plan, segment_reduce, segment_workspace  # noqa: F401
 from .histogram import HistogramConfig, bincount, histc, histogram_plan  # noqa: F401
 from .sort import SortConfig, argsort, group_by_key, sort, sort_plan  # noqa: F401
+from .topk import TopkConfig, topk, topk_plan  # noqa: F401
