@@ -28,6 +28,7 @@
 #include "mireduce/scan.hpp"
 #include "mireduce/segment.hpp"
 #include "mireduce/sort.hpp"
+#include "mireduce/select.hpp"
 #include "mireduce/topk.hpp"
 #include "mireduce/trace.hpp"
 #include "mireduce/types.hpp"
@@ -915,6 +916,69 @@ PYBIND11_MODULE(_C, m) {
         return topk_temp_bytes(rows, cols, k, static_cast<DType>(dtype));
       },
       py::arg("rows"), py::arg("cols"), py::arg("k"), py::arg("dtype"));
+  // Stream compaction (csrc/kernels/select.hip, csrc/runtime/select_cpu.cpp).
+  auto select_plan_dict = [](const SelectPlan& p) {
+    py::dict d;
+    d["block"] = p.block;
+    d["flag_bytes"] = p.flag_bytes;
+    d["tile_elems"] = p.tile_elems;
+    d["tiles"] = p.tiles;
+    d["tiles_per_wg"] = p.tiles_per_wg;
+    d["grid"] = p.grid;
+    d["launches"] = p.launches;
+    d["temp_bytes"] = p.temp_bytes;
+    d["data_head"] = p.data_head;
+    d["data_tail"] = p.data_tail;
+    d["mask_head"] = p.mask_head;
+    d["mask_tail"] = p.mask_tail;
+    d["max_grid"] = kSelectMaxGrid;
+    return d;
+  };
+  auto select_cfg = [](int max_blocks, int wg_per_cu) {
+    SelectConfig cfg;
+    cfg.max_blocks = max_blocks;
+    cfg.wg_per_cu = wg_per_cu;
+    return cfg;
+  };
+  auto select_mode = [](int mode, int dtype) {
+    MIREDUCE_REQUIRE(mode >= 0 && mode < kNumSelectModes, "select mode out of range");
+    MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+    return static_cast<SelectMode>(mode);
+  };
+  m.def(
+      "select",
+      [select_plan_dict, select_cfg, select_mode](int mode, uintptr_t x, int dtype, uintptr_t mask, uint64_t n, uint64_t capacity,
+                                                  uintptr_t out_values, uintptr_t out_idx, uintptr_t out_counts, uintptr_t count,
+                                                  uintptr_t temp, uint64_t temp_bytes, uintptr_t stream, int max_blocks, int wg_per_cu) {
+        return select_plan_dict(select(select_mode(mode, dtype), as_ptr<const void>(x), static_cast<DType>(dtype),
+                                       as_ptr<const uint8_t>(mask), n, capacity, as_ptr<void>(out_values), as_ptr<int64_t>(out_idx),
+                                       as_ptr<int64_t>(out_counts), as_ptr<int64_t>(count), as_ptr<void>(temp), temp_bytes,
+                                       as_stream(stream), select_cfg(max_blocks, wg_per_cu)));
+      },
+      py::arg("mode"), py::arg("x_ptr"), py::arg("dtype"), py::arg("mask_ptr"), py::arg("n"), py::arg("capacity"),
+      py::arg("out_values_ptr"), py::arg("out_idx_ptr"), py::arg("out_counts_ptr"), py::arg("count_ptr"), py::arg("temp_ptr"),
+      py::arg("temp_bytes"), py::arg("stream") = 0, py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0);
+  m.def(
+      "cpu_select",
+      [select_mode](int mode, uintptr_t x, int dtype, uintptr_t mask, uint64_t n, uint64_t capacity, uintptr_t out_values,
+                    uintptr_t out_idx, uintptr_t out_counts, uintptr_t count) {
+        const SelectMode sm = select_mode(mode, dtype);
+        py::gil_scoped_release nogil;
+        cpu_select(sm, as_ptr<const void>(x), static_cast<DType>(dtype), as_ptr<const uint8_t>(mask), n, capacity,
+                   as_ptr<void>(out_values), as_ptr<int64_t>(out_idx), as_ptr<int64_t>(out_counts), as_ptr<int64_t>(count));
+      },
+      py::arg("mode"), py::arg("x_ptr"), py::arg("dtype"), py::arg("mask_ptr"), py::arg("n"), py::arg("capacity"),
+      py::arg("out_values_ptr"), py::arg("out_idx_ptr"), py::arg("out_counts_ptr"), py::arg("count_ptr"));
+  m.def(
+      "select_plan",
+      [select_plan_dict, select_cfg, select_mode](int mode, uint64_t n, int dtype, bool want_counts, int num_cus, unsigned data_misalign,
+                                                  unsigned mask_misalign, int max_blocks, int wg_per_cu) {
+        return select_plan_dict(plan_select(select_mode(mode, dtype), n, static_cast<DType>(dtype), want_counts,
+                                            select_cfg(max_blocks, wg_per_cu), num_cus, data_misalign, mask_misalign));
+      },
+      py::arg("mode"), py::arg("n"), py::arg("dtype"), py::arg("want_counts") = false, py::arg("num_cus") = 256,
+      py::arg("data_misalign") = 0, py::arg("mask_misalign") = 0, py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0);
+  m.def("select_temp_bytes", [] { return select_temp_bytes(); });
   m.def(
       "moments",
       [](uintptr_t in, uint64_t n, int dtype, uintptr_t out5, uintptr_t partials, int max_grid, int num_cus,

@@ -14,3 +14,4 @@ from .segment import SegmentConfig, segment_plan, segment_reduce, segment_worksp
 from .histogram import HistogramConfig, bincount, histc, histogram_plan  # noqa: F401
 from .sort import SortConfig, argsort, group_by_key, sort, sort_plan  # noqa: F401
 from .topk import TopkConfig, topk, topk_plan  # noqa: F401
+from .select import SelectConfig, masked_select, nonzero, select_plan, unique, unique_consecutive  # noqa: F401
