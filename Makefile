@@ -166,7 +166,7 @@ $(BUILD)/bin/cpp_consumer: examples/cpp_consumer/main.cpp $(SHLIB) $(HEADERS)
 	$(HOSTCXX) $(HOSTFLAGS) $< $(LINK_BIN) $(LDLIBS) -o $@
 
 # Native unit tests (host code only) and the bootstrap multi-process test.
-UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/segment_unit $(BUILD)/bin/histogram_unit $(BUILD)/bin/sort_unit $(BUILD)/bin/topk_unit $(BUILD)/bin/select_unit $(BUILD)/bin/bootstrap_test
+UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/segment_unit $(BUILD)/bin/histogram_unit $(BUILD)/bin/sort_unit $(BUILD)/bin/topk_unit $(BUILD)/bin/select_unit $(BUILD)/bin/segscan_unit $(BUILD)/bin/bootstrap_test
 unit: $(UNIT)
 
 UNIT_SRCS := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
@@ -217,6 +217,13 @@ $(BUILD)/bin/select_unit: $(SELECT_UNIT_SRCS) $(HEADERS)
 	@mkdir -p $(dir $@)
 	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SELECT_UNIT_SRCS) -o $@
 
+# cpu_segment_scan against a naive double loop, the planner's invariants and the head helpers through which
+# the kernels read untrusted offsets (tests/native/segscan_unit.cpp; host code only).
+SEGSCAN_UNIT_SRCS := tests/native/segscan_unit.cpp csrc/runtime/segscan_cpu.cpp csrc/runtime/segment_cpu.cpp
+$(BUILD)/bin/segscan_unit: $(SEGSCAN_UNIT_SRCS) $(HEADERS)
+	@mkdir -p $(dir $@)
+	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SEGSCAN_UNIT_SRCS) -o $@
+
 $(BUILD)/bin/bootstrap_test: tests/native/bootstrap_test.cpp $(COMMLIB) $(SHLIB) $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(HOSTCXX) $(HOSTFLAGS) $< -Wl,--whole-archive $(COMMLIB) -Wl,--no-whole-archive $(LINK_BIN) \
@@ -242,6 +249,8 @@ asan: csrc/apps/reduce_mpi.cpp
 	    $(TOPK_UNIT_SRCS) -o $(BUILD)/asan/topk_unit
 	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
 	    $(SELECT_UNIT_SRCS) -o $(BUILD)/asan/select_unit
+	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
+	    $(SEGSCAN_UNIT_SRCS) -o $(BUILD)/asan/segscan_unit
 
 # Race detection: the threaded host reference reducers / arg-reductions under
 # ThreadSanitizer (tests/native/race_unit.cpp; exits non-zero on any report).

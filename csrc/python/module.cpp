@@ -27,6 +27,7 @@
 #include "mireduce/reduce_many.hpp"
 #include "mireduce/scan.hpp"
 #include "mireduce/segment.hpp"
+#include "mireduce/segscan.hpp"
 #include "mireduce/sort.hpp"
 #include "mireduce/select.hpp"
 #include "mireduce/topk.hpp"
@@ -686,6 +687,71 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"), py::arg("offsets_ptr"),
       py::arg("segments"), py::arg("out_ptr"));
+  // Batched and ragged prefix scans (csrc/kernels/segscan.hip, csrc/runtime/segscan_cpu.cpp).
+  auto segscan_plan_dict = [](const SegScanPlan& p) {
+    py::dict d;
+    d["block"] = p.block;
+    d["tile_elems"] = p.tile_elems;
+    d["tiles"] = p.tiles;
+    d["grid"] = p.grid;
+    d["tiles_per_wg"] = p.tiles_per_wg;
+    d["launches"] = p.launches;
+    d["vector_stores"] = p.vector_stores;
+    return d;
+  };
+  py::class_<SegScanWorkspace, std::shared_ptr<SegScanWorkspace>>(m, "SegScanWorkspace")
+      .def(py::init<int>(), py::arg("device") = -1)
+      .def_property_readonly("device", &SegScanWorkspace::device)
+      .def_property_readonly("num_cus", &SegScanWorkspace::num_cus);
+  m.def(
+      "segment_scan",
+      [segscan_plan_dict](SegScanWorkspace& ws, uintptr_t in, uint64_t n, int dtype, int op, int acc, int out_dtype,
+                          uintptr_t out, bool exclusive, uintptr_t offsets, uint64_t segments, uint64_t row_length,
+                          uintptr_t stream, int max_blocks, int wg_per_cu) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && acc >= 0 && acc < kNumDTypes && out_dtype >= 0 &&
+                             out_dtype < kNumDTypes && op >= 0 && op < kNumOps,
+                         "dtype / op out of range");
+        SegScanConfig cfg;
+        cfg.max_blocks = max_blocks;
+        cfg.wg_per_cu = wg_per_cu;
+        const SegScanSegments seg{as_ptr<const int64_t>(offsets), segments, row_length};
+        return segscan_plan_dict(segment_scan(as_ptr<const void>(in), n, static_cast<DType>(dtype), static_cast<Op>(op),
+                                              static_cast<DType>(acc), static_cast<DType>(out_dtype), as_ptr<void>(out),
+                                              exclusive, seg, ws, as_stream(stream), cfg));
+      },
+      py::arg("ws"), py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"),
+      py::arg("out_dtype"), py::arg("out_ptr"), py::arg("exclusive") = false, py::arg("offsets_ptr") = 0,
+      py::arg("segments") = 0, py::arg("row_length") = 0, py::arg("stream") = 0, py::arg("max_blocks") = 0,
+      py::arg("wg_per_cu") = 0);
+  m.def(
+      "segscan_plan",
+      [segscan_plan_dict](uintptr_t in, uintptr_t out, uint64_t n, int dtype, int out_dtype, int num_cus, int max_blocks,
+                          int wg_per_cu) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && out_dtype >= 0 && out_dtype < kNumDTypes,
+                         "dtype out of range");
+        SegScanConfig cfg;
+        cfg.max_blocks = max_blocks;
+        cfg.wg_per_cu = wg_per_cu;
+        return segscan_plan_dict(plan_segscan(as_ptr<const void>(in), as_ptr<const void>(out), n, static_cast<DType>(dtype),
+                                              static_cast<DType>(out_dtype), cfg, num_cus));
+      },
+      py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("dtype"), py::arg("out_dtype"),
+      py::arg("num_cus") = 256, py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0);
+  m.def(
+      "cpu_segment_scan",
+      [](uintptr_t in, uint64_t n, int dtype, int op, int acc, int out_dtype, uintptr_t out, bool exclusive,
+         uintptr_t offsets, uint64_t segments, uint64_t row_length) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && acc >= 0 && acc < kNumDTypes && out_dtype >= 0 &&
+                             out_dtype < kNumDTypes && op >= 0 && op < kNumOps,
+                         "dtype / op out of range");
+        py::gil_scoped_release nogil;
+        const SegScanSegments seg{as_ptr<const int64_t>(offsets), segments, row_length};
+        cpu_segment_scan(as_ptr<const void>(in), n, static_cast<DType>(dtype), static_cast<Op>(op), static_cast<DType>(acc),
+                         static_cast<DType>(out_dtype), as_ptr<void>(out), exclusive, seg);
+      },
+      py::arg("in_ptr"), py::arg("n"), py::arg("dtype"), py::arg("op"), py::arg("acc"), py::arg("out_dtype"),
+      py::arg("out_ptr"), py::arg("exclusive") = false, py::arg("offsets_ptr") = 0, py::arg("segments") = 0,
+      py::arg("row_length") = 0);
   // Histograms (csrc/kernels/histogram.hip, csrc/runtime/histogram_cpu.cpp).
   auto histogram_plan_dict = [](const HistogramPlan& p) {
     py::dict d;

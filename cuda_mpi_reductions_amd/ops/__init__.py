@@ -11,6 +11,7 @@ from .reduce_many import ReduceMany, norm_many, reduce_many  # noqa: F401
 from .arg_reduce import arg_reduce, argmax, argmin  # noqa: F401
 from .scan import ScanConfig, cummax, cummin, cumsum, scan, scan_plan, scan_workspace  # noqa: F401
 from .segment import SegmentConfig, segment_plan, segment_reduce, segment_workspace  # noqa: F401
+from .segment_scan import SegScanConfig, scan_dim, segment_scan, segscan_plan, segscan_workspace  # noqa: F401
 from .histogram import HistogramConfig, bincount, histc, histogram_plan  # noqa: F401
 from .sort import SortConfig, argsort, group_by_key, sort, sort_plan  # noqa: F401
 from .topk import TopkConfig, topk, topk_plan  # noqa: F401

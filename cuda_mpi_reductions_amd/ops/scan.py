@@ -1,8 +1,8 @@
 """Prefix scans (running reductions) of a contiguous tensor: ``cumsum`` / ``cummax`` / ``cummin``.
 
 ``scan(x, op)`` returns ``out[i] = x[0] ⊕ ... ⊕ x[i]`` (``exclusive=True``: up to ``x[i-1]``, so
-``out[0]`` is the carry) over the FLATTENED tensor; per-axis scans are out of scope (``x`` must be
-contiguous, and is viewed as 1-D). The rules are ``reduce``'s: integer sums wrap; float MIN / MAX
+``out[0]`` is the carry) over the FLATTENED tensor (``x`` must be contiguous, and is viewed as 1-D); for a
+scan of every row along the last axis see ``scan_dim``, for ragged segments ``segment_scan``. The rules are ``reduce``'s: integer sums wrap; float MIN / MAX
 ignore NaN, so a NaN leaves every prefix as if it were absent and a prefix made only of NaNs is the
 operator's identity (``torch.cummax`` / ``cummin`` propagate NaN instead); a float SUM prefix is NaN
 from the first NaN on. The output dtype is the accumulator dtype (``default_acc_dtype``: int32 SUM
