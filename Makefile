@@ -166,63 +166,30 @@ $(BUILD)/bin/cpp_consumer: examples/cpp_consumer/main.cpp $(SHLIB) $(HEADERS)
 	$(HOSTCXX) $(HOSTFLAGS) $< $(LINK_BIN) $(LDLIBS) -o $@
 
 # Native unit tests (host code only) and the bootstrap multi-process test.
-UNIT := $(BUILD)/bin/host_unit $(BUILD)/bin/scan_unit $(BUILD)/bin/segment_unit $(BUILD)/bin/histogram_unit $(BUILD)/bin/sort_unit $(BUILD)/bin/topk_unit $(BUILD)/bin/select_unit $(BUILD)/bin/segscan_unit $(BUILD)/bin/bootstrap_test
+# host_unit: the CLI / report / fault / combo helpers, without the ROCm headers. The per-feature units:
+# a host reference against a naive loop, the planner's invariants and the helpers through which the
+# kernels read untrusted input (tests/native/<name>_unit.cpp plus the runtime sources listed here).
+FEATURE_UNITS := scan segment histogram sort topk select segscan
+UNIT_SRCS_scan      := csrc/runtime/scan_cpu.cpp
+UNIT_SRCS_segment   := csrc/runtime/segment_cpu.cpp
+UNIT_SRCS_histogram := csrc/runtime/histogram_cpu.cpp
+UNIT_SRCS_sort      := csrc/runtime/sort_cpu.cpp csrc/runtime/histogram_cpu.cpp
+UNIT_SRCS_topk      := csrc/runtime/topk_cpu.cpp
+UNIT_SRCS_select    := csrc/runtime/select_cpu.cpp
+UNIT_SRCS_segscan   := csrc/runtime/segscan_cpu.cpp csrc/runtime/segment_cpu.cpp
+UNIT_SRCS_host      := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
+UNIT_FLAGS_host     := -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP
+UNIT_FLAGS_feature  := -Icsrc/include -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -DMIREDUCE_NO_HIP
+$(foreach u,$(FEATURE_UNITS),$(eval UNIT_FLAGS_$(u) := $(UNIT_FLAGS_feature)))
+ALL_UNITS := host $(FEATURE_UNITS)
+
+UNIT := $(foreach u,$(ALL_UNITS),$(BUILD)/bin/$(u)_unit) $(BUILD)/bin/bootstrap_test
 unit: $(UNIT)
 
-UNIT_SRCS := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
-$(BUILD)/bin/host_unit: tests/native/host_unit.cpp $(UNIT_SRCS) $(HEADERS)
+.SECONDEXPANSION:
+$(foreach u,$(ALL_UNITS),$(BUILD)/bin/$(u)_unit): $(BUILD)/bin/%_unit: tests/native/%_unit.cpp $$(UNIT_SRCS_$$*) $(HEADERS)
 	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP tests/native/host_unit.cpp \
-	    $(UNIT_SRCS) -o $@
-
-# cpu_scan against a naive loop (tests/native/scan_unit.cpp; host code only, as race_unit).
-SCAN_UNIT_SRCS := tests/native/scan_unit.cpp csrc/runtime/scan_cpu.cpp
-SCAN_UNIT_FLAGS := -Icsrc/include -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -DMIREDUCE_NO_HIP
-$(BUILD)/bin/scan_unit: $(SCAN_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SCAN_UNIT_SRCS) -o $@
-
-# cpu_segment_reduce against a naive loop, and the offset clamp / search helper of the kernels
-# (tests/native/segment_unit.cpp; host code only).
-SEGMENT_UNIT_SRCS := tests/native/segment_unit.cpp csrc/runtime/segment_cpu.cpp
-$(BUILD)/bin/segment_unit: $(SEGMENT_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SEGMENT_UNIT_SRCS) -o $@
-
-# The histogram binners at every edge, cpu_histogram against a naive loop and the planner's invariants
-# (tests/native/histogram_unit.cpp; host code only).
-HISTOGRAM_UNIT_SRCS := tests/native/histogram_unit.cpp csrc/runtime/histogram_cpu.cpp
-$(BUILD)/bin/histogram_unit: $(HISTOGRAM_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(HISTOGRAM_UNIT_SRCS) -o $@
-
-# The radix keys at every edge, cpu_sort / cpu_group_by_key against a naive stable insertion sort and the
-# planner's invariants (tests/native/sort_unit.cpp; host code only).
-SORT_UNIT_SRCS := tests/native/sort_unit.cpp csrc/runtime/sort_cpu.cpp csrc/runtime/histogram_cpu.cpp
-$(BUILD)/bin/sort_unit: $(SORT_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SORT_UNIT_SRCS) -o $@
-
-# cpu_topk against a naive O(n k) selection and the planner's invariants (tests/native/topk_unit.cpp; host
-# code only).
-TOPK_UNIT_SRCS := tests/native/topk_unit.cpp csrc/runtime/topk_cpu.cpp
-$(BUILD)/bin/topk_unit: $(TOPK_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(TOPK_UNIT_SRCS) -o $@
-
-# cpu_select against a naive loop and the planner's invariants (tests/native/select_unit.cpp; host code
-# only).
-SELECT_UNIT_SRCS := tests/native/select_unit.cpp csrc/runtime/select_cpu.cpp
-$(BUILD)/bin/select_unit: $(SELECT_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SELECT_UNIT_SRCS) -o $@
-
-# cpu_segment_scan against a naive double loop, the planner's invariants and the head helpers through which
-# the kernels read untrusted offsets (tests/native/segscan_unit.cpp; host code only).
-SEGSCAN_UNIT_SRCS := tests/native/segscan_unit.cpp csrc/runtime/segscan_cpu.cpp csrc/runtime/segment_cpu.cpp
-$(BUILD)/bin/segscan_unit: $(SEGSCAN_UNIT_SRCS) $(HEADERS)
-	@mkdir -p $(dir $@)
-	g++ $(CXXSTD) -O2 -Wall $(SCAN_UNIT_FLAGS) $(SEGSCAN_UNIT_SRCS) -o $@
+	g++ $(CXXSTD) -O2 -Wall $(UNIT_FLAGS_$*) $< $(UNIT_SRCS_$*) -o $@
 
 $(BUILD)/bin/bootstrap_test: tests/native/bootstrap_test.cpp $(COMMLIB) $(SHLIB) $(HEADERS)
 	@mkdir -p $(dir $@)
@@ -235,22 +202,8 @@ asan: csrc/apps/reduce_mpi.cpp
 	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP \
 	    -I$(MPI_HOME)/include $(MPI_SRCS) -static-libstdc++ -static-libgcc $(MPI_HOME)/lib/libmpi.so -Wl,-rpath,$(MPI_HOME)/lib \
 	    -o $(BUILD)/asan/reduce_mpi
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP \
-	    tests/native/host_unit.cpp $(UNIT_SRCS) -o $(BUILD)/asan/host_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(SCAN_UNIT_SRCS) -o $(BUILD)/asan/scan_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(SEGMENT_UNIT_SRCS) -o $(BUILD)/asan/segment_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(HISTOGRAM_UNIT_SRCS) -o $(BUILD)/asan/histogram_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(SORT_UNIT_SRCS) -o $(BUILD)/asan/sort_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(TOPK_UNIT_SRCS) -o $(BUILD)/asan/topk_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(SELECT_UNIT_SRCS) -o $(BUILD)/asan/select_unit
-	g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer $(SCAN_UNIT_FLAGS) \
-	    $(SEGSCAN_UNIT_SRCS) -o $(BUILD)/asan/segscan_unit
+	set -e; $(foreach u,$(ALL_UNITS),g++ $(CXXSTD) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $(UNIT_FLAGS_$(u)) tests/native/$(u)_unit.cpp $(UNIT_SRCS_$(u)) -o $(BUILD)/asan/$(u)_unit;)
 
 # Race detection: the threaded host reference reducers / arg-reductions under
 # ThreadSanitizer (tests/native/race_unit.cpp; exits non-zero on any report).

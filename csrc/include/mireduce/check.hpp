@@ -10,8 +10,9 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <stdexcept>
 #include <string>
+
+#include "mireduce/error.hpp"
 
 namespace mireduce {
 
@@ -19,12 +20,6 @@ namespace mireduce {
 using FatalHook = void (*)(int code);
 void set_fatal_hook(FatalHook hook);
 [[noreturn]] void fatal(const char* file, int line, const std::string& msg, int code = EXIT_FAILURE);
-
-// Library code throws (so the Python binding can turn errors into exceptions); apps use the
-// *_FATAL forms which print and exit like the reference.
-struct Error : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
 
 std::string hip_error_string(hipError_t e, const char* expr, const char* file, int line);
 

@@ -106,6 +106,21 @@ bool visit_combo(Op op, DType t, DType acc, F&& f) {
   return detail::visit_ops(Ops{}, op, t, acc, f);
 }
 
+// visit_combo<PlainOps> for the scans, which also choose an output type: calls f(Combo{}, OutT{}) with
+// OutT the accumulator, or the element type when out_t names it (scan_out_supported(), scan.hpp).
+template <class F>
+bool visit_scan_combo(Op op, DType t, DType acc, DType out_t, F&& f) {
+  return visit_combo<PlainOps>(op, t, acc, [&](auto c) {
+    using C = decltype(c);
+    if constexpr (std::is_same_v<typename C::elem, typename C::acc>) {
+      f(c, typename C::acc{});
+    } else {
+      if (out_t == t) f(c, typename C::elem{});
+      else f(c, typename C::acc{});
+    }
+  });
+}
+
 // Position in the list, at compile time (-1: not listed) and at run time.
 template <class OpT, class T, class AccT>
 constexpr int combo_position = detail::position<Combo<OpT, T, AccT>>(Combos{});

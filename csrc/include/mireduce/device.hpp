@@ -25,6 +25,9 @@ struct DeviceInfo {
 
 DeviceInfo device_info(int dev);
 int device_count();
+// Compute units of `device` (negative: the current device), asked once per device; 256 when the runtime
+// reports no positive count. What every planner's num_cus argument is fed from.
+int device_cus(int device = -1);
 
 class EventTimer {
  public:

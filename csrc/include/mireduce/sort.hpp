@@ -33,6 +33,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/histogram.hpp"
 #include "mireduce/ops.hpp"
@@ -113,6 +114,18 @@ template <> struct SortKeyTraits<float> { using U = uint32_t; static constexpr b
 template <> struct SortKeyTraits<double> { using U = uint64_t; static constexpr bool is_float = true; static constexpr U inf_bits = 0x7ff0000000000000ull; };
 template <> struct SortKeyTraits<bf16_t> { using U = uint16_t; static constexpr bool is_float = true; static constexpr U inf_bits = 0x7f80u; };
 template <> struct SortKeyTraits<f16_t> { using U = uint16_t; static constexpr bool is_float = true; static constexpr U inf_bits = 0x7c00u; };
+
+// The same table by run-time type: what the launchers of sort, topk and select put into their arguments.
+struct SortKeyFormat {
+  bool is_float = false;
+  uint64_t inf_bits = 0;
+};
+
+inline SortKeyFormat sort_key_format(DType t) {
+  SortKeyFormat f;
+  visit_dtype(t, [&](auto z) { f = {SortKeyTraits<decltype(z)>::is_float, SortKeyTraits<decltype(z)>::inf_bits}; });
+  return f;
+}
 
 template <class T>
 MIREDUCE_HD typename SortKeyTraits<T>::U sort_key(T v, bool descending = false) {

@@ -268,9 +268,7 @@ DirectAllreduce::DirectAllreduce(int device, size_t bytes, int grid, double time
   if (device < 0) MIREDUCE_HIP_THROW(hipGetDevice(&device));
   device_ = device;
   DeviceGuard g(device_);
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_));
-  grid_ = grid > 0 ? grid : std::max(1, cus);
+  grid_ = grid > 0 ? grid : device_cus(device_);
   MIREDUCE_REQUIRE(grid_ <= kMaxDirectBlocks, "direct: grid exceeds kMaxDirectBlocks");
   bytes_ = (std::max<size_t>(bytes, 16) + 255) / 256 * 256;
   // Fine-grained data buffers (peers read them over xGMI); uncached flags (polled while peers write).

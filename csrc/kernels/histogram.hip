@@ -28,6 +28,7 @@
 
 #include "mireduce/check.hpp"
 #include "mireduce/combo.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/histogram.hpp"
 #include "mireduce/vec16.hpp"
@@ -213,18 +214,6 @@ void launch_typed(const kern::HistArgs& a, const HistogramPlan& p, hipStream_t s
                                                                                          bins, a.out);
 }
 
-// Compute units of a device, asked once per device.
-int cus_of_current_device() {
-  static int cached[64] = {};
-  int device = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&device));
-  if (device >= 0 && device < 64 && cached[device]) return cached[device];
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (device >= 0 && device < 64) cached[device] = cus;
-  return cus;
-}
-
 }  // namespace
 
 HistogramPlan histogram(const void* in, uint64_t n, DType t, int64_t bins, double lo, double hi, int64_t* out,
@@ -236,7 +225,7 @@ HistogramPlan histogram(const void* in, uint64_t n, DType t, int64_t bins, doubl
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(in) % es == 0, "histogram: x must be aligned to its element size");
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(out) % 8 == 0 && reinterpret_cast<uintptr_t>(dropped) % 8 == 0,
                    "histogram: out / dropped must be 8-byte aligned");
-  const int cus = cus_of_current_device();
+  const int cus = device_cus();
   const kern::TileSpan sp = kern::tile_span(in, n, es);
   HistogramPlan p = plan_histogram(n ? sp.end : 0, bins, t, cfg, cus);
   if (!accumulate) {

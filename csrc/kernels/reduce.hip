@@ -183,9 +183,7 @@ Workspace::Workspace(int device, int max_grid, SlotMemory slot_memory) : max_gri
   MIREDUCE_REQUIRE(max_grid >= 1, "Workspace: max_grid must be positive");
   if (device < 0) MIREDUCE_HIP_THROW(hipGetDevice(&device));
   device_ = device;
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  num_cus_ = cus > 0 ? cus : 256;
+  num_cus_ = device_cus(device);
   const DeviceGuard guard(device);
   MIREDUCE_HIP_THROW(hipMalloc(&partials_, static_cast<size_t>(max_grid) * 8));
   // polled fan-in slots: uncached, so the finisher's polls see every XCD's stores. SlotMemory::Coarse

@@ -41,6 +41,7 @@
 #include "mireduce/device.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/scan.hpp"
 #include "mireduce/vec16.hpp"
 #include "reduce_kernels.hpp"
@@ -83,17 +84,6 @@ struct ScanArgs {
   int out_vec;            // vout is 16-byte aligned: whole vectors are stored 16 bytes at a time
 };
 
-template <class OpT, class AccT>
-__device__ __forceinline__ AccT wave_scan(AccT v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const AccT t = __shfl_up(v, off, 64);
-    if (lane >= off) v = OpT::apply(t, v);
-  }
-  return v;
-}
-
 // One thread's share of a tile: kScanVectors raw 16-byte vectors (identity where the array is not).
 template <class OpT, class T, class AccT>
 struct TileRegs {
@@ -102,7 +92,7 @@ struct TileRegs {
   V raw[kScanVectors];
 
   __device__ __forceinline__ static uint64_t vec_index(uint64_t tile, int u) {
-    return tile * kScanTileVecs + static_cast<uint64_t>(u) * kScanBlock + threadIdx.x;
+    return striped_vec(tile, u, kScanBlock, kScanTileVecs);
   }
   __device__ __forceinline__ static TileSpan span(const ScanArgs& a) { return {a.vin, a.pad, a.end}; }
 
@@ -163,6 +153,8 @@ __device__ __forceinline__ void tile_store(const ScanArgs& a, uint64_t tile, con
       run = OpT::apply(run, elem<T, AccT>(r.raw[u], k));
       o[k] = from_acc<OutT>(bad ? poisoned<OpT, AccT>() : (a.exclusive ? prev : run));
     }
+    // (its own clipped store, as segscan.hip's seg_tile: a shared store_clipped swapped the operands of the
+    // kernels' s_and_b64 masks, profiles/shared_prologue/, and nobody has measured that form)
     OutT* dst = reinterpret_cast<OutT*>(a.vout + v * (sizeof(OutT) * N));
     if (a.out_vec && whole<N>(TileRegs<OpT, T, AccT>::span(a), v)) {
       W w[kOutVecs];
@@ -196,8 +188,8 @@ __global__ void scan_empty(ScanArgs a) {
 template <class OpT, class T, class AccT>
 __global__ __launch_bounds__(kScanBlock) void scan_chunk_totals(ScanArgs a) {
   __shared__ AccT lds[kScanWaves];
-  const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * a.tiles_per_wg;
-  const uint64_t t1 = t0 + a.tiles_per_wg < a.ntiles ? t0 + a.tiles_per_wg : a.ntiles;
+  uint64_t t0, t1;
+  chunk_tiles(a.tiles_per_wg, a.ntiles, t0, t1);
   AccT acc = OpT::template identity<AccT>();
   for (uint64_t t = t0; t < t1; ++t) {
     TileRegs<OpT, T, AccT> r;
@@ -222,8 +214,8 @@ __global__ __launch_bounds__(kScanBlock) void scan_chunks(ScanArgs a) {
   if (threadIdx.x == 0) front = OpT::apply(load_carry<AccT>(a, ident), p);
   __syncthreads();
   AccT excl = front;
-  const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * a.tiles_per_wg;
-  const uint64_t t1 = t0 + a.tiles_per_wg < a.ntiles ? t0 + a.tiles_per_wg : a.ntiles;
+  uint64_t t0, t1;
+  chunk_tiles(a.tiles_per_wg, a.ntiles, t0, t1);
   for (uint64_t t = t0; t < t1; ++t) {
     TileRegs<OpT, T, AccT> r;
     AccT rel[kScanVectors];
@@ -416,20 +408,10 @@ void launch_typed(const kern::ScanArgs& a, const Launch& l) {
   }
 }
 
-template <class OpT, class T, class AccT>
-void launch_out(DType t, DType out_t, const kern::ScanArgs& a, const Launch& l) {
-  if constexpr (std::is_same_v<T, AccT>) {
-    launch_typed<OpT, T, AccT, AccT>(a, l);
-  } else {
-    if (out_t == t) launch_typed<OpT, T, AccT, T>(a, l);
-    else launch_typed<OpT, T, AccT, AccT>(a, l);
-  }
-}
-
 void launch_any(DType t, Op op, DType acc, DType out_t, const kern::ScanArgs& a, const Launch& l) {
-  const bool found = visit_combo<PlainOps>(op, t, acc, [&](auto c) {
+  const bool found = visit_scan_combo(op, t, acc, out_t, [&](auto c, auto o) {
     using C = decltype(c);
-    launch_out<typename C::op, typename C::elem, typename C::acc>(t, out_t, a, l);
+    launch_typed<typename C::op, typename C::elem, typename C::acc, decltype(o)>(a, l);
   });
   if (!found) throw Error("scan: no kernel for this (dtype, op, acc)");
 }
@@ -442,9 +424,7 @@ ScanWorkspace::ScanWorkspace(int device, int64_t max_tiles) : max_tiles_(max_til
   MIREDUCE_REQUIRE(max_tiles >= 1 && max_tiles <= (int64_t{1} << 24), "ScanWorkspace: max_tiles must be 1..2^24");
   if (device < 0) MIREDUCE_HIP_THROW(hipGetDevice(&device));
   device_ = device;
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  num_cus_ = cus > 0 ? cus : 256;
+  num_cus_ = device_cus(device);
   const DeviceGuard guard(device);
   const size_t desc_bytes = static_cast<size_t>(max_tiles) * 32;
   MIREDUCE_HIP_THROW(hipExtMallocWithFlags(reinterpret_cast<void**>(&desc_), desc_bytes, hipDeviceMallocUncached));
@@ -520,13 +500,7 @@ ScanPlan scan(const void* in, size_t n, DType t, Op op, DType acc, DType out_t, 
   MIREDUCE_REQUIRE(n == 0 || (in != nullptr && out != nullptr), "scan: null pointer");
   MIREDUCE_REQUIRE(carry_out == nullptr || carry_out != carry_in, "scan: carry_out must not be carry_in");
   const size_t es = dtype_size(t), os = dtype_size(out_t);
-  {
-    const char* i0 = static_cast<const char*>(in);
-    const char* o0 = static_cast<const char*>(out);
-    const bool overlap = n && i0 < o0 + n * os && o0 < i0 + n * es;
-    MIREDUCE_REQUIRE(!overlap || (i0 == o0 && es == os),
-                     "scan: out may be in (equal element sizes) but must not overlap it otherwise");
-  }
+  require_in_place_or_disjoint("scan", in, n * es, es, out, n * os, os);
   const ScanPlan p = plan_scan(in, out, n, t, out_t, cfg, ws.num_cus(), ws.max_tiles());
   const kern::TileSpan sp = kern::tile_span(in, n, es);
   kern::ScanArgs a{};

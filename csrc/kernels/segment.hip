@@ -242,9 +242,8 @@ __global__ __launch_bounds__(kSpanBlock) void segment_spans(SegArgs a, uint64_t 
   const SegmentOffsetsAt global_at{a.offsets};
   const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kSpanBlock / 64);
   for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * (kSpanBlock / 64) + (threadIdx.x >> 6); t < a.tiles; t += nwaves) {
-    const uint64_t v0 = t * tile_elems;
-    const uint64_t e0 = v0 > a.pad ? v0 - a.pad : 0;
-    const uint64_t e1 = v0 + tile_elems - a.pad < a.n ? v0 + tile_elems - a.pad : a.n;
+    uint64_t e0, e1;
+    tile_elements(a.pad, a.n, t, tile_elems, e0, e1);
     const int64_t s = segment_of(global_at, int64_t{0}, a.S - 1, a.n, e1 - 1);
     const uint64_t lo = segment_clamp(a.offsets[s], a.n), hi = segment_clamp(a.offsets[s + 1], a.n);
     if (lo < e0 || hi <= e1) continue;  // (wave-uniform) no segment begins here and runs past the end
@@ -324,9 +323,7 @@ SegmentWorkspace::SegmentWorkspace(int device, int64_t max_tiles) : max_tiles_(m
   MIREDUCE_REQUIRE(max_tiles >= 1 && max_tiles <= (int64_t{1} << 40), "SegmentWorkspace: max_tiles must be 1..2^40");
   if (device < 0) MIREDUCE_HIP_THROW(hipGetDevice(&device));
   device_ = device;
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  num_cus_ = cus > 0 ? cus : 256;
+  num_cus_ = device_cus(device);
   const DeviceGuard guard(device);
   MIREDUCE_HIP_THROW(hipMalloc(&pieces_, static_cast<size_t>(max_tiles) * 16));
 }

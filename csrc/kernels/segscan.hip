@@ -39,6 +39,7 @@
 #include "mireduce/device.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/segscan.hpp"
 #include "mireduce/vec16.hpp"
 #include "reduce_kernels.hpp"
@@ -71,14 +72,8 @@ struct SegScanArgs {
 };
 
 __device__ __forceinline__ TileSpan span_of(const SegScanArgs& a) { return {a.vin, a.pad, a.end}; }
-
-// Elements [e0, e1) of tile `tile`.
-__device__ __forceinline__ void tile_elements(const SegScanArgs& a, uint64_t tile, uint64_t tile_elems, uint64_t& e0,
-                                              uint64_t& e1) {
-  const uint64_t v0 = tile * tile_elems;
-  e0 = v0 > a.pad ? v0 - a.pad : 0;
-  e1 = v0 + tile_elems - a.pad < a.n ? v0 + tile_elems - a.pad : a.n;
-}
+// (The striped vector index is written out below, not tile_load.hpp's striped_vec: through the helper every
+// kernel here changed its registers and its instructions, profiles/shared_prologue/.)
 
 template <bool kRows>
 __device__ __forceinline__ SegScanTile tile_heads(const SegScanArgs& a, int64_t hint, uint64_t e0, uint64_t e1) {
@@ -95,14 +90,14 @@ __global__ __launch_bounds__(kScanBlock) void segscan_chunk_totals(SegScanArgs a
   __shared__ AccT lds[kSsWaves];
   const AccT ident = OpT::template identity<AccT>();
   const T ident_elem = from_acc<T>(ident);
-  const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * a.tiles_per_wg;
-  const uint64_t t1 = t0 + a.tiles_per_wg < a.tiles ? t0 + a.tiles_per_wg : a.tiles;
+  uint64_t t0, t1;
+  chunk_tiles(a.tiles_per_wg, a.tiles, t0, t1);
   AccT acc = ident;
   bool any = false;
   int64_t hint = 0;
   for (uint64_t t = t0; t < t1; ++t) {
     uint64_t e0, e1;
-    tile_elements(a, t, kTile, e0, e1);
+    tile_elements(a.pad, a.n, t, kTile, e0, e1);
     const SegScanTile st = tile_heads<kRows>(a, hint, e0, e1);
     hint = st.s_hi;
     V raw[kScanVectors];
@@ -239,7 +234,7 @@ __device__ __forceinline__ AccT seg_tile(const SegScanArgs& a, uint64_t tile, co
       run = OpT::apply(run, elem<T, AccT>(raw[u], k));
       o[k] = from_acc<OutT>(a.exclusive ? prev : run);
     }
-    OutT* dst = reinterpret_cast<OutT*>(a.vout + v * (sizeof(OutT) * N));
+    OutT* dst = reinterpret_cast<OutT*>(a.vout + v * (sizeof(OutT) * N));  // (its own clipped store: see scan.hip's tile_store)
     if (a.out_vec && whole<N>(span_of(a), v)) {
       W w[kOutVecs];
       __builtin_memcpy(w, o, sizeof(o));
@@ -286,12 +281,12 @@ __global__ __launch_bounds__(kScanBlock) void segscan_chunks(SegScanArgs a) {
   __syncthreads();
   AccT excl = s_front;
   const TileLds lds{s_off, s_row, s_has};
-  const uint64_t t0 = static_cast<uint64_t>(b) * a.tiles_per_wg;
-  const uint64_t t1 = t0 + a.tiles_per_wg < a.tiles ? t0 + a.tiles_per_wg : a.tiles;
+  uint64_t t0, t1;
+  chunk_tiles(a.tiles_per_wg, a.tiles, t0, t1);
   int64_t hint = 0;
   for (uint64_t t = t0; t < t1; ++t) {
     uint64_t e0, e1;
-    tile_elements(a, t, kTile, e0, e1);
+    tile_elements(a.pad, a.n, t, kTile, e0, e1);
     const SegScanTile st = tile_heads<kRows>(a, hint, e0, e1);
     hint = st.s_hi;
     if (st.has_head) excl = seg_tile<OpT, T, AccT, OutT, kRows, true>(a, t, st, e0, excl, lds);  // (workgroup-uniform)
@@ -323,20 +318,10 @@ void launch_typed(const kern::SegScanArgs& a, const Launch& l) {
   else launch_form<OpT, T, AccT, OutT, false>(a, l);
 }
 
-template <class OpT, class T, class AccT>
-void launch_out(DType t, DType out_t, const kern::SegScanArgs& a, const Launch& l) {
-  if constexpr (std::is_same_v<T, AccT>) {
-    launch_typed<OpT, T, AccT, AccT>(a, l);
-  } else {
-    if (out_t == t) launch_typed<OpT, T, AccT, T>(a, l);
-    else launch_typed<OpT, T, AccT, AccT>(a, l);
-  }
-}
-
 void launch_any(DType t, Op op, DType acc, DType out_t, const kern::SegScanArgs& a, const Launch& l) {
-  const bool found = visit_combo<PlainOps>(op, t, acc, [&](auto c) {
+  const bool found = visit_scan_combo(op, t, acc, out_t, [&](auto c, auto o) {
     using C = decltype(c);
-    launch_out<typename C::op, typename C::elem, typename C::acc>(t, out_t, a, l);
+    launch_typed<typename C::op, typename C::elem, typename C::acc, decltype(o)>(a, l);
   });
   if (!found) throw Error("segment_scan: no kernel for this (dtype, op, acc)");
 }
@@ -346,9 +331,7 @@ void launch_any(DType t, Op op, DType acc, DType out_t, const kern::SegScanArgs&
 SegScanWorkspace::SegScanWorkspace(int device) {
   if (device < 0) MIREDUCE_HIP_THROW(hipGetDevice(&device));
   device_ = device;
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  num_cus_ = cus > 0 ? cus : 256;
+  num_cus_ = device_cus(device);
   const DeviceGuard guard(device);
   MIREDUCE_HIP_THROW(hipMalloc(&partials_, static_cast<size_t>(kScanMaxGrid) * (8 + sizeof(unsigned))));
 }
@@ -367,13 +350,7 @@ SegScanPlan segment_scan(const void* in, uint64_t n, DType t, Op op, DType acc, 
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(seg.offsets) % 8 == 0, "segment_scan: offsets must be 8-byte aligned");
   MIREDUCE_REQUIRE(!rows || n % seg.row_length == 0, "segment_scan: row_length must divide the number of elements");
   const size_t es = dtype_size(t), os = dtype_size(out_t);
-  {
-    const char* i0 = static_cast<const char*>(in);
-    const char* o0 = static_cast<const char*>(out);
-    const bool overlap = n && i0 < o0 + n * os && o0 < i0 + n * es;
-    MIREDUCE_REQUIRE(!overlap || (i0 == o0 && es == os),
-                     "segment_scan: out may be in (equal element sizes) but must not overlap it otherwise");
-  }
+  require_in_place_or_disjoint("segment_scan", in, n * es, es, out, n * os, os);
   SegScanPlan p = plan_segscan(in, out, n, t, out_t, cfg, ws.num_cus());
   if (p.tiles == 0 || (!rows && seg.segments == 0)) {
     p.launches = 0;

@@ -34,6 +34,8 @@
 #include <cstdint>
 
 #include "mireduce/check.hpp"
+#include "mireduce/device.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/select.hpp"
 #include "tile_load.hpp"
 
@@ -132,8 +134,8 @@ __device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* lds) {
 template <class F, int kMode>
 __global__ __launch_bounds__(kSelectBlock) void select_count(SelectArgs a) {
   __shared__ uint64_t lds[kSelectWaves];
-  const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * a.tiles_per_wg;
-  const uint64_t t1 = t0 + a.tiles_per_wg < a.ntiles ? t0 + a.tiles_per_wg : a.ntiles;
+  uint64_t t0, t1;
+  chunk_tiles(a.tiles_per_wg, a.ntiles, t0, t1);
   uint64_t acc = 0;
   for (uint64_t t = t0; t < t1; ++t) {
     uint32_t c = 0;
@@ -161,8 +163,8 @@ __global__ __launch_bounds__(kSelectBlock) void select_scatter(SelectArgs a) {
   for (unsigned i = threadIdx.x; i < blockIdx.x; i += kSelectBlock) front += a.partials[i];
   uint64_t excl = block_sum(front, lds);  // selected elements in front of this workgroup's tiles
 
-  const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * a.tiles_per_wg;
-  const uint64_t t1 = t0 + a.tiles_per_wg < a.ntiles ? t0 + a.tiles_per_wg : a.ntiles;
+  uint64_t t0, t1;
+  chunk_tiles(a.tiles_per_wg, a.ntiles, t0, t1);
   U* out_values = static_cast<U*>(a.out_values);
   int buf = 0;
   for (uint64_t t = t0; t < t1; ++t, buf ^= 1) {
@@ -277,18 +279,6 @@ __global__ __launch_bounds__(kSelectRunBlock) void select_run_counts(const int64
 
 namespace {
 
-// Compute units of a device, asked once per device.
-int select_cus_of_current_device() {
-  static int cached[64] = {};
-  int device = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&device));
-  if (device >= 0 && device < 64 && cached[device]) return cached[device];
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (device >= 0 && device < 64) cached[device] = cus;
-  return cus;
-}
-
 template <class U, class F, int kMode>
 void launch(const kern::SelectArgs& a, const SelectPlan& p, hipStream_t stream) {
   kern::select_count<F, kMode><<<p.grid, kSelectBlock, 0, stream>>>(a);
@@ -302,11 +292,6 @@ void launch_mode(SelectMode mode, const kern::SelectArgs& a, const SelectPlan& p
     case SelectMode::Nonzero: launch<U, U, static_cast<int>(SelectMode::Nonzero)>(a, p, stream); break;
     case SelectMode::RunHeads: launch<U, U, static_cast<int>(SelectMode::RunHeads)>(a, p, stream); break;
   }
-}
-
-bool overlaps(const void* x, size_t xb, const void* y, size_t yb) {
-  const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
-  return x && y && xb && yb && x0 < y0 + yb && y0 < x0 + xb;
 }
 
 }  // namespace
@@ -328,15 +313,16 @@ SelectPlan select(SelectMode mode, const void* x, DType t, const uint8_t* mask, 
     MIREDUCE_HIP_THROW(hipMemsetAsync(count, 0, 8, stream));
     return plan_select(mode, n, t, out_counts != nullptr, cfg, 256, data_mis, mask_mis);
   }
-  const SelectPlan p = plan_select(mode, n, t, out_counts != nullptr, cfg, select_cus_of_current_device(), data_mis, mask_mis);
+  const SelectPlan p = plan_select(mode, n, t, out_counts != nullptr, cfg, device_cus(), data_mis, mask_mis);
   MIREDUCE_REQUIRE(temp != nullptr && reinterpret_cast<uintptr_t>(temp) % 8 == 0 && temp_bytes >= p.temp_bytes,
                    "select: the temporary must be 8-byte aligned and hold select_temp_bytes()");
   const void* const ins[2] = {x, mask};
   const size_t in_bytes[2] = {n * es, n};
   for (int s = 0; s < 2; ++s) {
-    MIREDUCE_REQUIRE(!overlaps(ins[s], in_bytes[s], out_values, capacity * es) && !overlaps(ins[s], in_bytes[s], out_idx, capacity * 8) &&
-                         !overlaps(ins[s], in_bytes[s], out_counts, capacity * 8) && !overlaps(ins[s], in_bytes[s], count, 8) &&
-                         !overlaps(ins[s], in_bytes[s], temp, p.temp_bytes),
+    MIREDUCE_REQUIRE(!ranges_overlap(ins[s], in_bytes[s], out_values, capacity * es) &&
+                         !ranges_overlap(ins[s], in_bytes[s], out_idx, capacity * 8) &&
+                         !ranges_overlap(ins[s], in_bytes[s], out_counts, capacity * 8) &&
+                         !ranges_overlap(ins[s], in_bytes[s], count, 8) && !ranges_overlap(ins[s], in_bytes[s], temp, p.temp_bytes),
                      "select: the input and the mask must overlap neither an output nor the temporary");
   }
   kern::SelectArgs a{};
@@ -345,13 +331,9 @@ SelectPlan select(SelectMode mode, const void* x, DType t, const uint8_t* mask, 
   a.ntiles = p.tiles;
   a.tiles_per_wg = p.tiles_per_wg;
   a.capacity = capacity;
-  switch (t) {
-    case DType::Float32: a.is_float = 1; a.inf_bits = SortKeyTraits<float>::inf_bits; break;
-    case DType::Float64: a.is_float = 1; a.inf_bits = SortKeyTraits<double>::inf_bits; break;
-    case DType::BFloat16: a.is_float = 1; a.inf_bits = SortKeyTraits<bf16_t>::inf_bits; break;
-    case DType::Float16: a.is_float = 1; a.inf_bits = SortKeyTraits<f16_t>::inf_bits; break;
-    default: break;
-  }
+  const SortKeyFormat kf = sort_key_format(t);
+  a.is_float = kf.is_float ? 1 : 0;
+  a.inf_bits = kf.inf_bits;
   a.out_values = out_values;
   a.out_idx = out_idx;
   a.count = count;

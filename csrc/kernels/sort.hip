@@ -34,8 +34,11 @@
 #include <cstdint>
 
 #include "mireduce/check.hpp"
+#include "mireduce/device.hpp"
 #include "mireduce/histogram.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/sort.hpp"
+#include "tile_load.hpp"
 
 namespace mireduce {
 namespace kern {
@@ -88,8 +91,8 @@ __global__ __launch_bounds__(kSortBlock) void sort_count(SortArgs a) {
   __shared__ uint32_t s_count[256];
   if (threadIdx.x < 256) s_count[threadIdx.x] = 0;
   __syncthreads();
-  const uint32_t first = blockIdx.x * a.tiles_per_wg;
-  const uint32_t stop = min(first + a.tiles_per_wg, a.tiles);
+  uint32_t first, stop;
+  chunk_tiles(a.tiles_per_wg, a.tiles, first, stop);
   for (uint32_t tile = first; tile < stop; ++tile) {
     const uint32_t base = tile * kSortTile;  // tiles * 4096 <= n + 4095 < 2^32
 #pragma unroll
@@ -116,6 +119,8 @@ __global__ __launch_bounds__(kSortScanBlock) void sort_scan_table(uint32_t* tabl
       v[k] = i0 + k < entries ? table[i0 + k] : 0u;
       sum += v[k];
     }
+    // (the wave scan is written out here and in sort_scatter, not tile_load.hpp's wave_inclusive_sum: through
+    // the helper both kernels came out with other instructions, profiles/shared_prologue/)
     uint32_t incl = sum;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -156,8 +161,8 @@ __global__ __launch_bounds__(kSortBlock) void sort_scatter(SortArgs a) {
   if (threadIdx.x < 256) s_base[threadIdx.x] = threadIdx.x < digits ? a.table[threadIdx.x * gridDim.x + blockIdx.x] : 0u;
   const uint64_t below = (uint64_t{1} << lane) - 1;
 
-  const uint32_t first = blockIdx.x * a.tiles_per_wg;
-  const uint32_t stop = min(first + a.tiles_per_wg, a.tiles);
+  uint32_t first, stop;
+  chunk_tiles(a.tiles_per_wg, a.tiles, first, stop);
   for (uint32_t tile = first; tile < stop; ++tile) {
     const uint32_t base = tile * kSortTile;
     const uint32_t valid_tile = min(a.n - base, kSortTile);
@@ -263,18 +268,6 @@ __global__ __launch_bounds__(kSortBlock) void sort_scatter(SortArgs a) {
 
 namespace {
 
-// Compute units of a device, asked once per device.
-int cus_of_current_device() {
-  static int cached[64] = {};
-  int device = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&device));
-  if (device >= 0 && device < 64 && cached[device]) return cached[device];
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (device >= 0 && device < 64) cached[device] = cus;
-  return cus;
-}
-
 template <class U, bool kIdx>
 void launch_pass(const kern::SortArgs& a, const SortPlan& p, hipStream_t stream) {
   kern::sort_count<U><<<p.grid, kSortBlock, 0, stream>>>(a);
@@ -331,18 +324,13 @@ kern::SortArgs common_args(const void* in, uint64_t n, const SortPlan& p, void* 
   return a;
 }
 
-bool overlaps(const void* x, size_t xb, const void* y, size_t yb) {
-  const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
-  return xb && yb && x0 < y0 + yb && y0 < x0 + xb;
-}
-
 }  // namespace
 
 SortPlan sort(const void* in, uint64_t n, DType t, bool descending, void* out_keys, int64_t* out_idx, void* temp,
               size_t temp_bytes, hipStream_t stream, const SortConfig& cfg) {
   sort_check_args(n, t);
   const bool with_idx = out_idx != nullptr;
-  const SortPlan p = plan_sort(n, t, with_idx, cfg, cus_of_current_device());
+  const SortPlan p = plan_sort(n, t, with_idx, cfg, device_cus());
   if (n == 0) return p;
   const size_t es = dtype_size(t);
   MIREDUCE_REQUIRE(in != nullptr && out_keys != nullptr && temp != nullptr, "sort: null pointer");
@@ -351,8 +339,8 @@ SortPlan sort(const void* in, uint64_t n, DType t, bool descending, void* out_ke
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(out_idx) % 8 == 0, "sort: indices must be 8-byte aligned");
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(temp) % 16 == 0 && temp_bytes >= p.temp_bytes,
                    "sort: the temporary must be 16-byte aligned and hold sort_temp_bytes()");
-  MIREDUCE_REQUIRE(!overlaps(in, n * es, out_keys, n * es) && !overlaps(in, n * es, out_idx, with_idx ? n * 8 : 0) &&
-                       !overlaps(in, n * es, temp, p.temp_bytes),
+  MIREDUCE_REQUIRE(!ranges_overlap(in, n * es, out_keys, n * es) && !ranges_overlap(in, n * es, out_idx, n * 8) &&
+                       !ranges_overlap(in, n * es, temp, p.temp_bytes),
                    "sort: the input must overlap neither an output nor the temporary");
   Buffers b{};
   b.keys_out = out_keys;
@@ -362,14 +350,9 @@ SortPlan sort(const void* in, uint64_t n, DType t, bool descending, void* out_ke
   b.idx_tmp = reinterpret_cast<uint32_t*>(static_cast<char*>(temp) + p.temp_idx);
   kern::SortArgs a = common_args(in, n, p, temp);
   a.flip = descending ? ~uint64_t{0} : 0;
-  int mode = kern::kInSigned;
-  switch (t) {
-    case DType::Float32: mode = kern::kInFloat; a.inf_bits = SortKeyTraits<float>::inf_bits; break;
-    case DType::Float64: mode = kern::kInFloat; a.inf_bits = SortKeyTraits<double>::inf_bits; break;
-    case DType::BFloat16: mode = kern::kInFloat; a.inf_bits = SortKeyTraits<bf16_t>::inf_bits; break;
-    case DType::Float16: mode = kern::kInFloat; a.inf_bits = SortKeyTraits<f16_t>::inf_bits; break;
-    default: break;
-  }
+  const SortKeyFormat kf = sort_key_format(t);
+  const int mode = kf.is_float ? kern::kInFloat : kern::kInSigned;
+  a.inf_bits = kf.inf_bits;
   run_passes(p, b, a, mode, mode, stream);
   return p;
 }
@@ -379,14 +362,14 @@ SortPlan group_by_key(const void* ids, uint64_t n, DType t, int64_t bins, int64_
   sort_check_args(n, t);
   MIREDUCE_REQUIRE(t == DType::Int32 || t == DType::Int64, "group_by_key: ids must be int32 or int64");
   histogram(ids, n, t, bins, 0.0, 1.0, counts, dropped, false, stream);  // checks bins, ids and the two outputs
-  const SortPlan p = plan_sort(n, t, true, cfg, cus_of_current_device(), sort_group_key_bits(bins));
+  const SortPlan p = plan_sort(n, t, true, cfg, device_cus(), sort_group_key_bits(bins));
   if (n == 0) return p;
   const size_t es = dtype_size(t);
   MIREDUCE_REQUIRE(order != nullptr && temp != nullptr, "group_by_key: null pointer");
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(order) % 8 == 0, "group_by_key: order must be 8-byte aligned");
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(temp) % 16 == 0 && temp_bytes >= p.temp_bytes,
                    "group_by_key: the temporary must be 16-byte aligned and hold sort_temp_bytes()");
-  MIREDUCE_REQUIRE(!overlaps(ids, n * es, order, n * 8) && !overlaps(ids, n * es, temp, p.temp_bytes),
+  MIREDUCE_REQUIRE(!ranges_overlap(ids, n * es, order, n * 8) && !ranges_overlap(ids, n * es, temp, p.temp_bytes),
                    "group_by_key: ids must overlap neither the order nor the temporary");
   Buffers b{};
   b.keys_out = nullptr;  // the sorted keys are not asked for

@@ -35,7 +35,10 @@
 #include <cstdint>
 
 #include "mireduce/check.hpp"
+#include "mireduce/device.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/topk.hpp"
+#include "tile_load.hpp"
 
 namespace mireduce {
 namespace kern {
@@ -224,12 +227,7 @@ __device__ __forceinline__ void pick_digit(const uint32_t* s_hist, uint32_t rema
       c[i] = s_hist[lane * 4 + i];
       sum += c[i];
     }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
+    const uint32_t incl = wave_inclusive_sum(sum);
     uint32_t run = incl - sum;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -529,18 +527,6 @@ __global__ __launch_bounds__(kTopkBlock) void topk_split_finish(TopkSplitArgs a)
 
 namespace {
 
-// Compute units of a device, asked once per device.
-int topk_cus_of_current_device() {
-  static int cached[64] = {};
-  int device = 0;
-  MIREDUCE_HIP_THROW(hipGetDevice(&device));
-  if (device >= 0 && device < 64 && cached[device]) return cached[device];
-  int cus = 0;
-  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (device >= 0 && device < 64) cached[device] = cus;
-  return cus;
-}
-
 struct TopkCall {
   const void* in;
   uint64_t rows;
@@ -601,18 +587,13 @@ void launch(const TopkCall& c, const TopkPlan& p) {
   kern::topk_split_finish<U><<<row_grid, kTopkBlock, 0, c.stream>>>(a);
 }
 
-bool overlaps(const void* x, size_t xb, const void* y, size_t yb) {
-  const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
-  return xb && yb && x0 < y0 + yb && y0 < x0 + xb;
-}
-
 }  // namespace
 
 TopkPlan topk(const void* in, uint64_t rows, uint64_t cols, int64_t k, DType t, bool largest, void* out_values,
               int64_t* out_idx, void* temp, size_t temp_bytes, hipStream_t stream, const TopkConfig& cfg) {
   topk_check_args(rows, cols, k, t);
   if (rows == 0 || k == 0) return plan_topk(rows, cols, k, t, cfg, 256);
-  const TopkPlan p = plan_topk(rows, cols, k, t, cfg, topk_cus_of_current_device());
+  const TopkPlan p = plan_topk(rows, cols, k, t, cfg, device_cus());
   const size_t es = dtype_size(t);
   MIREDUCE_REQUIRE(in != nullptr && out_values != nullptr && out_idx != nullptr, "topk: null pointer");
   MIREDUCE_REQUIRE(reinterpret_cast<uintptr_t>(in) % es == 0 && reinterpret_cast<uintptr_t>(out_values) % es == 0,
@@ -621,8 +602,8 @@ TopkPlan topk(const void* in, uint64_t rows, uint64_t cols, int64_t k, DType t, 
   MIREDUCE_REQUIRE(p.temp_bytes == 0 || (temp != nullptr && reinterpret_cast<uintptr_t>(temp) % 16 == 0 && temp_bytes >= p.temp_bytes),
                    "topk: the temporary must be 16-byte aligned and hold topk_temp_bytes()");
   const size_t in_bytes = rows * cols * es, out_elems = rows * static_cast<uint64_t>(k);
-  MIREDUCE_REQUIRE(!overlaps(in, in_bytes, out_values, out_elems * es) && !overlaps(in, in_bytes, out_idx, out_elems * 8) &&
-                       !overlaps(in, in_bytes, temp, p.temp_bytes),
+  MIREDUCE_REQUIRE(!ranges_overlap(in, in_bytes, out_values, out_elems * es) && !ranges_overlap(in, in_bytes, out_idx, out_elems * 8) &&
+                       !ranges_overlap(in, in_bytes, temp, p.temp_bytes),
                    "topk: the input must overlap neither an output nor the temporary");
   TopkCall c{};
   c.in = in;
@@ -630,13 +611,9 @@ TopkPlan topk(const void* in, uint64_t rows, uint64_t cols, int64_t k, DType t, 
   c.cols = static_cast<uint32_t>(cols);
   c.k = static_cast<uint32_t>(k);
   c.kf.flip = largest ? ~uint64_t{0} : 0;
-  switch (t) {
-    case DType::Float32: c.kf.is_float = 1; c.kf.inf_bits = SortKeyTraits<float>::inf_bits; break;
-    case DType::Float64: c.kf.is_float = 1; c.kf.inf_bits = SortKeyTraits<double>::inf_bits; break;
-    case DType::BFloat16: c.kf.is_float = 1; c.kf.inf_bits = SortKeyTraits<bf16_t>::inf_bits; break;
-    case DType::Float16: c.kf.is_float = 1; c.kf.inf_bits = SortKeyTraits<f16_t>::inf_bits; break;
-    default: break;
-  }
+  const SortKeyFormat kf = sort_key_format(t);
+  c.kf.is_float = kf.is_float ? 1 : 0;
+  c.kf.inf_bits = kf.inf_bits;
   c.out_values = out_values;
   c.out_idx = out_idx;
   c.temp = temp;

@@ -1,6 +1,8 @@
 // Device helpers; see device.hpp.
 #include "mireduce/device.hpp"
 
+#include <atomic>
+
 namespace mireduce {
 
 DeviceInfo device_info(int dev) {
@@ -20,6 +22,18 @@ int device_count() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
+}
+
+int device_cus(int device) {
+  static std::atomic<int> cached[64];  // 0: not asked yet (racing first calls store the same value)
+  if (device < 0) MIREDUCE_HIP_THROW(hipGetDevice(&device));
+  std::atomic<int>* const slot = device < 64 ? &cached[device] : nullptr;
+  int cus = slot ? slot->load(std::memory_order_relaxed) : 0;
+  if (cus > 0) return cus;
+  MIREDUCE_HIP_THROW(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  if (cus <= 0) cus = 256;
+  if (slot) slot->store(cus, std::memory_order_relaxed);
+  return cus;
 }
 
 EventTimer::EventTimer() {

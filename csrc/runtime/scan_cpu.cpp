@@ -7,6 +7,7 @@
 #include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/scan.hpp"
 
 namespace mireduce {
@@ -49,17 +50,6 @@ void scan_typed(const T* in, size_t n, OutT* out, bool exclusive, const A* carry
   if (carry_out) *carry_out = run.value();
 }
 
-template <class OpT, class T, class A>
-void scan_out(DType t, DType out_t, const void* in, size_t n, void* out, bool exclusive, const void* ci, void* co) {
-  const T* i = static_cast<const T*>(in);
-  const A* c0 = static_cast<const A*>(ci);
-  A* c1 = static_cast<A*>(co);
-  if constexpr (!std::is_same_v<T, A>) {
-    if (out_t == t) return scan_typed<OpT, T, A, T>(i, n, static_cast<T*>(out), exclusive, c0, c1);
-  }
-  scan_typed<OpT, T, A, A>(i, n, static_cast<A*>(out), exclusive, c0, c1);
-}
-
 }  // namespace
 
 void cpu_scan(const void* in, size_t n, DType t, Op op, DType acc, DType out_t, void* out, bool exclusive,
@@ -68,17 +58,15 @@ void cpu_scan(const void* in, size_t n, DType t, Op op, DType acc, DType out_t, 
   MIREDUCE_REQUIRE(acc_supported(t, op, acc), "scan: unsupported accumulator for this dtype / op");
   MIREDUCE_REQUIRE(scan_out_supported(t, acc, out_t), "scan: the output type is the accumulator or the input type");
   MIREDUCE_REQUIRE(n == 0 || (in != nullptr && out != nullptr), "scan: null pointer");
-  {
-    const char* i0 = static_cast<const char*>(in);
-    const char* o0 = static_cast<const char*>(out);
-    const size_t es = dtype_size(t), os = dtype_size(out_t);
-    const bool overlap = n && i0 < o0 + n * os && o0 < i0 + n * es;
-    MIREDUCE_REQUIRE(!overlap || (i0 == o0 && es == os),
-                     "scan: out may be in (equal element sizes) but must not overlap it otherwise");
-  }
-  visit_combo<PlainOps>(op, t, acc, [&](auto c) {  // found: acc_supported() above
+  const size_t es = dtype_size(t), os = dtype_size(out_t);
+  require_in_place_or_disjoint("scan", in, n * es, es, out, n * os, os);
+  visit_scan_combo(op, t, acc, out_t, [&](auto c, auto o) {  // found: acc_supported() above
     using C = decltype(c);
-    scan_out<typename C::op, typename C::elem, typename C::acc>(t, out_t, in, n, out, exclusive, carry_in, carry_out);
+    using T = typename C::elem;
+    using A = typename C::acc;
+    using OutT = decltype(o);
+    scan_typed<typename C::op, T, A, OutT>(static_cast<const T*>(in), n, static_cast<OutT*>(out), exclusive,
+                                           static_cast<const A*>(carry_in), static_cast<A*>(carry_out));
   });
 }
 

@@ -9,6 +9,7 @@
 #include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/segscan.hpp"
 
 namespace mireduce {
@@ -59,15 +60,6 @@ void scan_typed(const T* in, uint64_t n, OutT* out, bool exclusive, const SegSca
   }
 }
 
-template <class OpT, class T, class A>
-void scan_out(DType t, DType out_t, const void* in, uint64_t n, void* out, bool exclusive, const SegScanSegments& seg) {
-  const T* i = static_cast<const T*>(in);
-  if constexpr (!std::is_same_v<T, A>) {
-    if (out_t == t) return scan_typed<OpT, T, A, T>(i, n, static_cast<T*>(out), exclusive, seg);
-  }
-  scan_typed<OpT, T, A, A>(i, n, static_cast<A*>(out), exclusive, seg);
-}
-
 }  // namespace
 
 // Host code (the native unit test checks its invariants): the tiles are those of the virtual index space
@@ -116,17 +108,13 @@ void cpu_segment_scan(const void* in, uint64_t n, DType t, Op op, DType acc, DTy
       throw Error("segment_scan: " + at + " must be the number of elements " + std::to_string(n));
     }
   }
-  {
-    const char* i0 = static_cast<const char*>(in);
-    const char* o0 = static_cast<const char*>(out);
-    const size_t es = dtype_size(t), os = dtype_size(out_t);
-    const bool overlap = n && i0 < o0 + n * os && o0 < i0 + n * es;
-    MIREDUCE_REQUIRE(!overlap || (i0 == o0 && es == os),
-                     "segment_scan: out may be in (equal element sizes) but must not overlap it otherwise");
-  }
-  visit_combo<PlainOps>(op, t, acc, [&](auto c) {  // found: acc_supported() above
+  const size_t es = dtype_size(t), os = dtype_size(out_t);
+  require_in_place_or_disjoint("segment_scan", in, n * es, es, out, n * os, os);
+  visit_scan_combo(op, t, acc, out_t, [&](auto c, auto o) {  // found: acc_supported() above
     using C = decltype(c);
-    scan_out<typename C::op, typename C::elem, typename C::acc>(t, out_t, in, n, out, exclusive, seg);
+    using T = typename C::elem;
+    using OutT = decltype(o);
+    scan_typed<typename C::op, T, typename C::acc, OutT>(static_cast<const T*>(in), n, static_cast<OutT*>(out), exclusive, seg);
   });
 }
 

@@ -5,10 +5,12 @@
 #include <cstdint>
 #include <cstdio>
 #include <limits>
+#include <string>
 #include <vector>
 
 #include "mireduce/check.hpp"
 #include "mireduce/half.hpp"
+#include "mireduce/ranges.hpp"
 #include "mireduce/scan.hpp"
 
 using namespace mireduce;
@@ -147,7 +149,66 @@ static void check_errors() {
   CHECK(total == 3.f);  // n == 0: the total is the carry
 }
 
+// ranges_overlap / require_in_place_or_disjoint (ranges.hpp): what every launcher and host reference asks.
+static void check_ranges() {
+  alignas(8) char buf[64];
+  CHECK(!ranges_overlap(buf, 16, buf + 32, 16));  // disjoint
+  CHECK(!ranges_overlap(buf + 32, 16, buf, 16));
+  CHECK(!ranges_overlap(buf, 16, buf + 16, 16));  // touching at the boundary
+  CHECK(!ranges_overlap(buf + 16, 16, buf, 16));
+  CHECK(ranges_overlap(buf, 17, buf + 16, 16));   // one byte shared
+  CHECK(ranges_overlap(buf + 16, 16, buf, 17));
+  CHECK(ranges_overlap(buf, 16, buf, 16));        // identical
+  CHECK(ranges_overlap(buf, 64, buf + 8, 1));     // one inside the other
+  CHECK(!ranges_overlap(nullptr, 16, buf, 16));   // null or empty on either side
+  CHECK(!ranges_overlap(buf, 16, nullptr, 16));
+  CHECK(!ranges_overlap(nullptr, 16, nullptr, 16));
+  CHECK(!ranges_overlap(buf, 0, buf, 16));
+  CHECK(!ranges_overlap(buf, 16, buf, 0));
+
+  const auto message = [&](const char* who, const void* in, size_t ib, size_t es, const void* out, size_t ob, size_t os) {
+    try {
+      require_in_place_or_disjoint(who, in, ib, es, out, ob, os);
+    } catch (const Error& e) {
+      return std::string(e.what());
+    }
+    return std::string();
+  };
+  const std::string text = "scan: out may be in (equal element sizes) but must not overlap it otherwise";
+  CHECK(message("scan", buf, 16, 4, buf + 32, 16, 4).empty());    // disjoint
+  CHECK(message("scan", buf, 16, 4, buf + 16, 32, 8).empty());    // touching
+  CHECK(message("scan", buf, 32, 4, buf, 32, 4).empty());         // in place, equal element sizes
+  CHECK(message("scan", buf, 16, 4, buf, 32, 8) == text);         // the same start, a wider output
+  CHECK(message("scan", buf, 32, 8, buf, 16, 4) == text);         // the same start, a narrower output
+  CHECK(message("scan", buf, 20, 4, buf + 16, 16, 4) == text);    // a shared tail
+  CHECK(message("scan", buf + 4, 16, 4, buf, 16, 4) == text);     // shifted by one element
+  CHECK(message("scan", nullptr, 16, 4, buf, 16, 4).empty());     // null or empty on either side
+  CHECK(message("scan", buf, 16, 4, nullptr, 16, 4).empty());
+  CHECK(message("scan", buf, 0, 4, buf, 0, 8).empty());
+  CHECK(message("scan", buf, 0, 4, buf, 16, 8).empty());
+  CHECK(message("scan", buf, 16, 4, buf, 0, 8).empty());
+  CHECK(message("segment_scan", buf, 16, 4, buf + 8, 16, 4) ==
+        "segment_scan: out may be in (equal element sizes) but must not overlap it otherwise");
+  // the host reference words it the same way
+  std::vector<float> v(9);
+  std::string got;
+  try {
+    cpu_scan(v.data(), 8, DType::Float32, Op::Sum, DType::Float32, DType::Float32, v.data() + 1, false, nullptr, nullptr);
+  } catch (const Error& e) {
+    got = e.what();
+  }
+  CHECK(got == text);
+  got.clear();
+  try {  // the same address, a wider output
+    cpu_scan(v.data(), 4, DType::Float32, Op::Sum, DType::Float64, DType::Float64, v.data(), false, nullptr, nullptr);
+  } catch (const Error& e) {
+    got = e.what();
+  }
+  CHECK(got == text);
+}
+
 int main() {
+  check_ranges();
   for (size_t n : {size_t{0}, size_t{1}, size_t{2}, size_t{63}, size_t{1000}}) {
     check_int<int32_t, int32_t>(DType::Int32, DType::Int32, n);
     check_int<int32_t, int64_t>(DType::Int32, DType::Int64, n);

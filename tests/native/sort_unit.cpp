@@ -255,7 +255,21 @@ static void check_plan() {
   CHECK(throws([&] { cpu_group_by_key(f, 2, DType::Float32, 2, out, out + 2, out + 3); }));
 }
 
+// sort_key_format: the run-time view of SortKeyTraits that the launchers of sort, topk and select use.
+template <class T>
+static void check_key_format(DType t) {
+  const SortKeyFormat f = sort_key_format(t);
+  CHECK(f.is_float == SortKeyTraits<T>::is_float);
+  CHECK(f.inf_bits == static_cast<uint64_t>(SortKeyTraits<T>::inf_bits));
+}
+
 int main() {
+  check_key_format<int32_t>(DType::Int32);
+  check_key_format<int64_t>(DType::Int64);
+  check_key_format<float>(DType::Float32);
+  check_key_format<double>(DType::Float64);
+  check_key_format<bf16_t>(DType::BFloat16);
+  check_key_format<f16_t>(DType::Float16);
   check_integer_keys<int32_t>();
   check_integer_keys<int64_t>();
   check_float_keys<float>();
