@@ -27,13 +27,13 @@
 #include "mireduce/check.hpp"
 #include "mireduce/combo.hpp"
 #include "mireduce/half.hpp"
+#include "mireduce/row_layout.hpp"
 #include "mireduce/vec16.hpp"
+#include "row_stream.hpp"
 
 namespace mireduce {
 namespace kern {
 
-constexpr int kArgBlock = 256;
-constexpr int kArgUnroll = 8;      // short rows: row batches per wave trip
 constexpr int kArgLongUnroll = 4;  // long rows: default vectors in flight per lane (tile = U x 256)
 constexpr int64_t kNoIndex = std::numeric_limits<int64_t>::max();
 constexpr uint32_t kNoTrip = 0xffffffffu;
@@ -143,11 +143,84 @@ __device__ __forceinline__ void block_fold(K& v, int64_t& i, K* lv, int64_t* li)
   }
 }
 
-template <class V>
-__device__ V g_arg_dummy_vec;  // readable 16 bytes for predicated-off vector loads
+// The running bests of one lane of the long-row and wave-per-row kernels: P slot groups x N vector
+// slots, each with the trip number at which it last improved (see the head of this file). A tile is U
+// vectors per lane; vector u of the lane's m-th tile is trip m * U + u and goes to slot group u % P.
+template <bool MAX, class T, int U>
+struct ArgSlots {
+  using K = typename ArgKey<T>::type;
+  using C = ArgCmp<MAX, K>;
+  using V = typename Vec16<T>::type;
+  static constexpr int N = Vec16<T>::N;
+  static constexpr int P = N >= 8 ? 1 : (8 / N < U ? 8 / N : U);  // P * N running bests per lane
+  static_assert(U % P == 0, "slot groups must divide the unroll");
+  K best[P][N];
+  uint32_t trip[P][N];
 
-// Row batches per wave trip of the 16-byte short-row kernel: M x batches vectors in flight per lane.
-constexpr int short_vec_batches(int m) { return m >= 4 ? 4 : kArgUnroll; }
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        best[q][k] = C::identity();
+        trip[q][k] = kNoTrip;
+      }
+  }
+
+  // A full tile.
+  __device__ __forceinline__ void take(const V (&v)[U], uint32_t m) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        const K x = elem<T, K>(v[u], k);
+        const bool w = C::beats(x, best[u % P][k]);
+        best[u % P][k] = w ? x : best[u % P][k];
+        trip[u % P][k] = w ? m * U + u : trip[u % P][k];
+      }
+    }
+  }
+
+  // A predicated tile: vector u counts only where ok(u).
+  template <class Ok>
+  __device__ __forceinline__ void take(const V (&v)[U], uint32_t m, Ok ok_of) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool ok = ok_of(u);
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        const K x = elem<T, K>(v[u], k);
+        const bool w = ok && C::beats(x, best[u % P][k]);
+        best[u % P][k] = w ? x : best[u % P][k];
+        trip[u % P][k] = w ? m * U + u : trip[u % P][k];
+      }
+    }
+  }
+
+  // Slot bests become (value, index) pairs and fold into (bv, bi); index_of(trip, k) is the element's index.
+  template <class IndexOf>
+  __device__ __forceinline__ void resolve(IndexOf index_of, K& bv, int64_t& bi) const {
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        if (trip[q][k] == kNoTrip) continue;
+        const int64_t idx = index_of(trip[q][k], k);
+        if (C::pair_beats(best[q][k], idx, bv, bi)) {
+          bv = best[q][k];
+          bi = idx;
+        }
+      }
+  }
+};
+
+// Row r's answer. No element registered (the sentinel index, the largest value of I): every element of
+// the row equals the identity -> index 0.
+template <class T, class K, class I>
+__device__ __forceinline__ void write_result(const ArgArgs& a, uint64_t r, K bv, I bi) {
+  static_cast<T*>(a.out_value)[r] = key_to_elem<T, K>(bv);
+  a.out_index[r] = bi == std::numeric_limits<I>::max() ? 0 : static_cast<int64_t>(bi);
+}
 
 // Long rows: the `splits` workgroups of a row interleave over its tiles of kArgUnroll x kArgBlock
 // vectors (workgroup s takes tiles s, s + splits, ...), so at any moment the grid streams one
@@ -160,8 +233,6 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
   constexpr uint64_t kTile = static_cast<uint64_t>(U) * kArgBlock;  // vectors per tile
-  constexpr int P = N >= 8 ? 1 : (8 / N < U ? 8 / N : U);  // slot groups: P * N running bests per lane
-  static_assert(U % P == 0, "slot groups must divide the unroll");
   constexpr int kWaves = kArgBlock / 64;
   __shared__ K lv[kWaves];
   __shared__ int64_t li[kWaves];
@@ -174,9 +245,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
     const uint64_t r = seg / S;
     const uint64_t s = seg % S;
     const T* p = base + r * a.cols;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
-    uint64_t head = addr % 16 ? (16 - addr % 16) / sizeof(T) : 0;
-    if (head > a.cols) head = a.cols;
+    const uint64_t head = head_elems(p, 0, a.cols);
     const uint64_t nvec = (a.cols - head) / N;
     const uint64_t tb = head + nvec * N;  // scalar tail [tb, cols)
     const uint64_t nfull = nvec / kTile, ntiles = (nvec + kTile - 1) / kTile;
@@ -192,15 +261,8 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
         bi = tid;
       }
     }
-    K best[P][N];
-    uint32_t trip[P][N];  // q = m * U + u: the u-th vector of this workgroup's m-th tile
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        best[q][k] = C::identity();
-        trip[q][k] = kNoTrip;
-      }
+    ArgSlots<MAX, T, U> slots;  // trip m * U + u: the u-th vector of this workgroup's m-th tile
+    slots.init();
     uint64_t tile = s;
     uint32_t m = 0;
     for (; tile < nfull; tile += S, ++m) {
@@ -209,16 +271,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(tp + static_cast<uint64_t>(u) * kArgBlock);
       __builtin_amdgcn_sched_barrier(0);  // all loads out before the first compare
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const K x = elem<T, K>(v[u], k);
-          const bool w = C::beats(x, best[u % P][k]);
-          best[u % P][k] = w ? x : best[u % P][k];
-          trip[u % P][k] = w ? m * U + u : trip[u % P][k];
-        }
-      }
+      slots.take(v, m);
     }
     if (tile < ntiles) {  // the partial last tile is this workgroup's turn
       const uint64_t j0 = tile * kTile + tid;
@@ -226,34 +279,18 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint64_t j = j0 + static_cast<uint64_t>(u) * kArgBlock;
-        v[u] = __builtin_nontemporal_load(j < nvec ? vp + j : &g_arg_dummy_vec<V>);
+        v[u] = __builtin_nontemporal_load(j < nvec ? vp + j : &dummy_vec<V>);
       }
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool ok = j0 + static_cast<uint64_t>(u) * kArgBlock < nvec;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const K x = elem<T, K>(v[u], k);
-          const bool w = ok && C::beats(x, best[u % P][k]);
-          best[u % P][k] = w ? x : best[u % P][k];
-          trip[u % P][k] = w ? m * U + u : trip[u % P][k];
-        }
-      }
+      slots.take(v, m, [&](int u) { return j0 + static_cast<uint64_t>(u) * kArgBlock < nvec; });
     }
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        if (trip[q][k] == kNoTrip) continue;
-        const uint64_t mt = trip[q][k] / U, u = trip[q][k] % U;
-        const uint64_t j = (s + mt * S) * kTile + u * kArgBlock + tid;
-        const int64_t idx = static_cast<int64_t>(head + j * N + k);
-        if (C::pair_beats(best[q][k], idx, bv, bi)) {
-          bv = best[q][k];
-          bi = idx;
-        }
-      }
+    slots.resolve(
+        [&](uint32_t trip, int k) {
+          const uint64_t mt = trip / U, u = trip % U;
+          const uint64_t j = (s + mt * S) * kTile + u * kArgBlock + tid;
+          return static_cast<int64_t>(head + j * N + k);
+        },
+        bv, bi);
     if (s == S - 1 && static_cast<uint64_t>(tid) < a.cols - tb) {
       const K x = load_key<T, K>(p + tb + tid);
       const int64_t idx = static_cast<int64_t>(tb + tid);
@@ -264,19 +301,12 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
     }
     block_fold<MAX, K>(bv, bi, lv, li);
     if (S == 1) {
-      if (tid == 0) {
-        // no element registered: every element of the row equals the identity -> index 0
-        static_cast<T*>(a.out_value)[r] = key_to_elem<T, K>(bv);
-        a.out_index[r] = bi == kNoIndex ? 0 : bi;
-      }
+      if (tid == 0) write_result<T>(a, r, bv, bi);
     } else {
       if (tid == 0) {
         store_sc1(&a.partials[2 * seg], key_bits(bv));
         store_sc1(&a.partials[2 * seg + 1], static_cast<uint64_t>(bi));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned prev = __hip_atomic_fetch_add(&a.tickets[r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == S - 1;
-        if (last) __hip_atomic_store(&a.tickets[r], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = take_ticket(a.tickets, r, S);
       }
       __syncthreads();
       if (last) {  // last workgroup of row r: every lane folds a share of the row's partials
@@ -292,10 +322,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_rows_kernel(ArgArgs a) {
           }
         }
         block_fold<MAX, K>(fv, fi, lv, li);
-        if (tid == 0) {
-          static_cast<T*>(a.out_value)[r] = key_to_elem<T, K>(fv);
-          a.out_index[r] = fi == kNoIndex ? 0 : fi;
-        }
+        if (tid == 0) write_result<T>(a, r, fv, fi);
       }
     }
     __syncthreads();  // lv/li/last are rewritten by the next segment
@@ -311,16 +338,13 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
   constexpr uint64_t kTile = static_cast<uint64_t>(U) * 64;
-  constexpr int P = N >= 8 ? 1 : (8 / N < U ? 8 / N : U);
   const int lane = threadIdx.x & 63;
   const uint64_t wave = (static_cast<uint64_t>(blockIdx.x) * kArgBlock + threadIdx.x) / 64;
   const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kArgBlock / 64);
   const T* base = static_cast<const T*>(a.in);
   for (uint64_t r = wave; r < a.rows; r += nwaves) {  // wave-uniform
     const T* p = base + r * a.cols;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
-    uint64_t head = addr % 16 ? (16 - addr % 16) / sizeof(T) : 0;
-    if (head > a.cols) head = a.cols;
+    const uint64_t head = head_elems(p, 0, a.cols);
     const uint64_t nvec = (a.cols - head) / N;
     const uint64_t tb = head + nvec * N;
     const uint64_t nfull = nvec / kTile;
@@ -334,15 +358,8 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
         bi = lane;
       }
     }
-    K best[P][N];
-    uint32_t trip[P][N];  // q = tile * U + u: vector q * 64 + lane
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        best[q][k] = C::identity();
-        trip[q][k] = kNoTrip;
-      }
+    ArgSlots<MAX, T, U> slots;  // trip q = tile * U + u: vector q * 64 + lane
+    slots.init();
     uint32_t tile = 0;
     for (; tile < nfull; ++tile) {
       const V* tp = vp + tile * kTile + lane;
@@ -350,16 +367,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(tp + u * 64);
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const K x = elem<T, K>(v[u], k);
-          const bool w = C::beats(x, best[u % P][k]);
-          best[u % P][k] = w ? x : best[u % P][k];
-          trip[u % P][k] = w ? tile * U + u : trip[u % P][k];
-        }
-      }
+      slots.take(v, tile);
     }
     if (static_cast<uint64_t>(tile) * kTile < nvec) {  // partial last tile, predicated
       const uint64_t j0 = static_cast<uint64_t>(tile) * kTile + lane;
@@ -367,32 +375,14 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint64_t j = j0 + static_cast<uint64_t>(u) * 64;
-        v[u] = __builtin_nontemporal_load(j < nvec ? vp + j : &g_arg_dummy_vec<V>);
+        v[u] = __builtin_nontemporal_load(j < nvec ? vp + j : &dummy_vec<V>);
       }
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool ok = j0 + static_cast<uint64_t>(u) * 64 < nvec;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const K x = elem<T, K>(v[u], k);
-          const bool w = ok && C::beats(x, best[u % P][k]);
-          best[u % P][k] = w ? x : best[u % P][k];
-          trip[u % P][k] = w ? tile * U + u : trip[u % P][k];
-        }
-      }
+      slots.take(v, tile, [&](int u) { return j0 + static_cast<uint64_t>(u) * 64 < nvec; });
     }
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        if (trip[q][k] == kNoTrip) continue;
-        const int64_t idx = static_cast<int64_t>(head + (static_cast<uint64_t>(trip[q][k]) * 64 + lane) * N + k);
-        if (C::pair_beats(best[q][k], idx, bv, bi)) {
-          bv = best[q][k];
-          bi = idx;
-        }
-      }
+    slots.resolve(
+        [&](uint32_t trip, int k) { return static_cast<int64_t>(head + (static_cast<uint64_t>(trip) * 64 + lane) * N + k); },
+        bv, bi);
     if (static_cast<uint64_t>(lane) < a.cols - tb) {
       const K x = load_key<T, K>(p + tb + lane);
       const int64_t idx = static_cast<int64_t>(tb + lane);
@@ -402,10 +392,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_wave_rows_kernel(ArgArgs a) {
       }
     }
     wave_fold<MAX, K>(bv, bi, 64);
-    if (lane == 0) {
-      static_cast<T*>(a.out_value)[r] = key_to_elem<T, K>(bv);
-      a.out_index[r] = bi == kNoIndex ? 0 : bi;
-    }
+    if (lane == 0) write_result<T>(a, r, bv, bi);
   }
 }
 
@@ -419,16 +406,11 @@ __global__ __launch_bounds__(kArgBlock) void arg_short_vec_kernel(ArgArgs a) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
   constexpr int U = short_vec_batches(M);
-  const int lane = threadIdx.x & 63;
-  const int lpr = a.lpr;
-  const int per_wave = 64 / lpr;
-  const int sub = lane / lpr, sl = lane % lpr;
+  const LaneGroups g = lane_groups<kArgBlock, U>(a.lpr);
+  const int lpr = g.lpr, per_wave = g.per_wave, sub = g.sub, sl = g.sl;
   const uint64_t vecs = a.cols / N;
-  const uint64_t wave = (static_cast<uint64_t>(blockIdx.x) * kArgBlock + threadIdx.x) / 64;
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kArgBlock / 64);
-  const uint64_t per_trip = static_cast<uint64_t>(per_wave) * U;
   const V* base = static_cast<const V*>(a.in);
-  for (uint64_t r0 = wave * per_trip; r0 < a.rows; r0 += nwaves * per_trip) {  // wave-uniform
+  for (uint64_t r0 = g.first; r0 < a.rows; r0 += g.stride) {  // wave-uniform
     V v[U][M];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -437,7 +419,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_short_vec_kernel(ArgArgs a) {
       for (int mm = 0; mm < M; ++mm) {
         const uint64_t c = static_cast<uint64_t>(sl) + static_cast<uint64_t>(mm) * lpr;
         const bool ok = r < a.rows && c < vecs;
-        v[u][mm] = __builtin_nontemporal_load(ok ? base + r * vecs + c : &g_arg_dummy_vec<V>);
+        v[u][mm] = __builtin_nontemporal_load(ok ? base + r * vecs + c : &dummy_vec<V>);
       }
     }
     __builtin_amdgcn_sched_barrier(0);  // all loads out before the first compare
@@ -460,10 +442,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_short_vec_kernel(ArgArgs a) {
         }
       }
       wave_fold<MAX, K, uint32_t>(bv, bi, lpr);
-      if (sl == 0 && r < a.rows) {
-        static_cast<T*>(a.out_value)[r] = key_to_elem<T, K>(bv);
-        a.out_index[r] = bi == kNoIndex32 ? 0 : static_cast<int64_t>(bi);
-      }
+      if (sl == 0 && r < a.rows) write_result<T>(a, r, bv, bi);
     }
   }
 }
@@ -475,15 +454,10 @@ __global__ __launch_bounds__(kArgBlock) void arg_short_kernel(ArgArgs a) {
   using K = typename ArgKey<T>::type;
   using C = ArgCmp<MAX, K>;
   constexpr int U = kArgUnroll;
-  const int lane = threadIdx.x & 63;
-  const int lpr = a.lpr;
-  const int per_wave = 64 / lpr;
-  const int sub = lane / lpr, sl = lane % lpr;
-  const uint64_t wave = (static_cast<uint64_t>(blockIdx.x) * kArgBlock + threadIdx.x) / 64;
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kArgBlock / 64);
-  const uint64_t per_trip = static_cast<uint64_t>(per_wave) * U;
+  const LaneGroups g = lane_groups<kArgBlock, U>(a.lpr);
+  const int lpr = g.lpr, per_wave = g.per_wave, sub = g.sub, sl = g.sl;
   const T* base = static_cast<const T*>(a.in);
-  for (uint64_t r0 = wave * per_trip; r0 < a.rows; r0 += nwaves * per_trip) {  // wave-uniform
+  for (uint64_t r0 = g.first; r0 < a.rows; r0 += g.stride) {  // wave-uniform
     K x[U][M];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -510,10 +484,7 @@ __global__ __launch_bounds__(kArgBlock) void arg_short_kernel(ArgArgs a) {
         }
       }
       wave_fold<MAX, K, uint32_t>(bv, bi, lpr);
-      if (sl == 0 && r < a.rows) {
-        static_cast<T*>(a.out_value)[r] = key_to_elem<T, K>(bv);
-        a.out_index[r] = bi == kNoIndex32 ? 0 : static_cast<int64_t>(bi);
-      }
+      if (sl == 0 && r < a.rows) write_result<T>(a, r, bv, bi);
     }
   }
 }
@@ -550,67 +521,7 @@ __global__ void loc_pick_kernel(const uint64_t* __restrict__ pairs, int world, i
 
 namespace {
 
-constexpr int kMaxResident = 8;
-constexpr uint64_t kMaxArgSplits = 4096;
-constexpr uint64_t kShortCols = 256;        // scalar lane-group rows (any alignment)
-constexpr uint64_t kShortVecBytes = 4096;   // 16-byte lane-group rows (aligned)
-constexpr uint64_t kWaveRowBytes = 65536;   // wave-per-row rows
-
-uint64_t next_pow2_u(uint64_t v) {
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-// Kernel variants: 0 long rows; 1, 2, 4 scalar short rows (M columns per lane); 11, 12 vector
-// short rows (M = 1, 2, 4 vectors per lane); 20 medium rows (a wave per row).
-enum Variant : int { kLong = 0, kScalar1 = 1, kScalar2 = 2, kScalar4 = 4, kVec1 = 11, kVec2 = 12, kVec4 = 14, kWave = 20 };
-
-int variant_of(const void* in, uint64_t cols, DType t) {
-  const uint64_t es = dtype_size(t), bytes = cols * es;
-  if (reinterpret_cast<uintptr_t>(in) % 16 == 0 && bytes % 16 == 0 && bytes <= kShortVecBytes)
-    return bytes / 16 <= 64 ? kVec1 : bytes / 16 <= 128 ? kVec2 : kVec4;
-  if (cols <= kShortCols) return cols <= 64 ? kScalar1 : cols <= 128 ? kScalar2 : kScalar4;
-  return bytes <= kWaveRowBytes ? kWave : kLong;
-}
-
-struct ArgLayout {
-  int lpr = kern::kArgBlock;  // short rows: lanes per row
-  uint64_t splits = 1;        // long rows: workgroups per row
-  int grid = 1;
-};
-
-ArgLayout arg_layout(int variant, uint64_t rows, uint64_t cols, DType t, int num_cus, int resident, int unroll) {
-  ArgLayout L;
-  const uint64_t N = 16 / dtype_size(t);
-  const uint64_t target = static_cast<uint64_t>(num_cus) * resident;  // resident workgroups
-  uint64_t blocks;
-  if (variant == kWave) {
-    blocks = (rows + 3) / 4;
-  } else if (variant != kLong) {
-    const uint64_t units = variant >= kVec1 ? cols / N : cols;  // vectors or elements per row
-    const uint64_t m = variant >= kVec1 ? variant - 10 : variant;
-    L.lpr = static_cast<int>(std::min<uint64_t>(64, next_pow2_u(std::max<uint64_t>((units + m - 1) / m, 1))));
-    const uint64_t batches = variant >= kVec1 ? kern::short_vec_batches(static_cast<int>(m)) : kern::kArgUnroll;
-    const uint64_t per_trip = static_cast<uint64_t>(64 / L.lpr) * batches;
-    const uint64_t waves = (rows + per_trip - 1) / per_trip;
-    blocks = (waves + 3) / 4;
-  } else {
-    const uint64_t tiles = std::max<uint64_t>(1, (cols / N) / (static_cast<uint64_t>(unroll) * kern::kArgBlock));
-    const uint64_t want = (target + rows - 1) / rows;
-    L.splits = std::max<uint64_t>(1, std::min({want, tiles, kMaxArgSplits}));
-    blocks = rows * L.splits;
-  }
-  L.grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(blocks, target)));
-  return L;
-}
-
-template <class Kern>
-int resident_of(Kern k) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kern::kArgBlock, 0) != hipSuccess || n < 1) n = 1;
-  return std::min(n, kMaxResident);
-}
+using namespace layout;
 
 using ArgFn = void (*)(const kern::ArgArgs&, int variant, int unroll, int grid, hipStream_t);
 using ArgOccFn = int (*)(int variant, int unroll);
@@ -640,18 +551,18 @@ void launch_arg(const kern::ArgArgs& a, int variant, int unroll, int grid, hipSt
 
 template <bool MAX, class T>
 int arg_resident(int variant, int unroll) {
-  static const int occ_long[3] = {resident_of(kern::arg_rows_kernel<MAX, T, 2>), resident_of(kern::arg_rows_kernel<MAX, T, 4>),
-                                  resident_of(kern::arg_rows_kernel<MAX, T, 8>)};
-  static const int occ_wave[3] = {resident_of(kern::arg_wave_rows_kernel<MAX, T, 2>),
-                                  resident_of(kern::arg_wave_rows_kernel<MAX, T, 4>),
-                                  resident_of(kern::arg_wave_rows_kernel<MAX, T, 8>)};
-  static const int occ_vec4 = resident_of(kern::arg_short_vec_kernel<MAX, T, 4>);
+  static const int occ_long[3] = {resident_workgroups(kern::arg_rows_kernel<MAX, T, 2>, kern::kArgBlock), resident_workgroups(kern::arg_rows_kernel<MAX, T, 4>, kern::kArgBlock),
+                                  resident_workgroups(kern::arg_rows_kernel<MAX, T, 8>, kern::kArgBlock)};
+  static const int occ_wave[3] = {resident_workgroups(kern::arg_wave_rows_kernel<MAX, T, 2>, kern::kArgBlock),
+                                  resident_workgroups(kern::arg_wave_rows_kernel<MAX, T, 4>, kern::kArgBlock),
+                                  resident_workgroups(kern::arg_wave_rows_kernel<MAX, T, 8>, kern::kArgBlock)};
+  static const int occ_vec4 = resident_workgroups(kern::arg_short_vec_kernel<MAX, T, 4>, kern::kArgBlock);
   static const int occ[6] = {0,
-                             resident_of(kern::arg_short_kernel<MAX, T, 1>),
-                             resident_of(kern::arg_short_kernel<MAX, T, 2>),
-                             resident_of(kern::arg_short_kernel<MAX, T, 4>),
-                             resident_of(kern::arg_short_vec_kernel<MAX, T, 1>),
-                             resident_of(kern::arg_short_vec_kernel<MAX, T, 2>)};
+                             resident_workgroups(kern::arg_short_kernel<MAX, T, 1>, kern::kArgBlock),
+                             resident_workgroups(kern::arg_short_kernel<MAX, T, 2>, kern::kArgBlock),
+                             resident_workgroups(kern::arg_short_kernel<MAX, T, 4>, kern::kArgBlock),
+                             resident_workgroups(kern::arg_short_vec_kernel<MAX, T, 1>, kern::kArgBlock),
+                             resident_workgroups(kern::arg_short_vec_kernel<MAX, T, 2>, kern::kArgBlock)};
   switch (variant) {
     case kLong: return occ_long[unroll == 2 ? 0 : unroll == 8 ? 2 : 1];
     case kWave: return occ_wave[unroll == 2 ? 0 : unroll == 8 ? 2 : 1];
@@ -699,24 +610,10 @@ void launch_loc_pick(const uint64_t* pairs, int world, bool max, int64_t* out_in
                           static_cast<T*>(out_value));
 }
 
-size_t ticket_bytes(uint64_t rows) { return (rows * sizeof(unsigned) + 255) / 256 * 256; }
-
-// Split rows have rows < target = num_cus x resident <= num_cus x kMaxResident (arg_layout), so
-// the per-row tickets of EVERY split launch fit one fixed region at the start of the scratch and
-// the partials always start after it. A row-count-dependent boundary would let a later call with
-// more rows read an earlier call's partial bits as tickets (the kernels leave only tickets zero).
-size_t ticket_region_bytes(int num_cus) {
-  return ticket_bytes(static_cast<uint64_t>(num_cus) * kMaxResident);
-}
-
 }  // namespace
 
 size_t arg_reduce_scratch_bytes(size_t rows, size_t cols, DType t, int num_cus) {
-  // Only long rows split, and the most splits any occupancy gives bounds every launch (rows short
-  // enough for the lane-group kernels have a single tile, hence no splits either way).
-  const ArgLayout L = arg_layout(kLong, rows, cols, t, num_cus, kMaxResident, 2);
-  if (L.splits <= 1) return 0;
-  return ticket_region_bytes(num_cus) + rows * L.splits * 16;
+  return arg_scratch_bytes(rows, cols, t, num_cus);
 }
 
 ArgPlan arg_reduce_rows(const void* in, size_t rows, size_t cols, DType t, Op op, void* out_value, int64_t* out_index,
@@ -763,7 +660,7 @@ ArgPlan arg_reduce_rows(const void* in, size_t rows, size_t cols, DType t, Op op
     MIREDUCE_REQUIRE(scratch != nullptr, "arg_reduce: this shape needs scratch (arg_reduce_scratch_bytes)");
     MIREDUCE_REQUIRE(rows < static_cast<size_t>(num_cus) * kMaxResident, "arg_reduce: split rows exceed the ticket region");
     a.tickets = static_cast<unsigned*>(scratch);
-    a.partials = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + ticket_region_bytes(num_cus));
+    a.partials = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + arg_ticket_region_bytes(num_cus));
   }
   e.fn(a, variant, unroll, L.grid, stream);
   MIREDUCE_HIP_THROW(hipGetLastError());

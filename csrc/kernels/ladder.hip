@@ -20,6 +20,7 @@
 #include "mireduce/combo.hpp"
 #include "mireduce/ladder.hpp"
 #include "mireduce/ops.hpp"
+#include "mireduce/row_layout.hpp"
 
 namespace mireduce {
 namespace ladder {
@@ -142,13 +143,6 @@ __global__ __launch_bounds__(BLOCK) void k6(const Tin* __restrict__ in, uint64_t
   unrolled_tail<BLOCK, OpT>(sdata, v, out);
 }
 
-uint64_t next_pow2(uint64_t x) {
-  if (x <= 1) return 1;
-  --x;
-  for (int s = 1; s < 64; s <<= 1) x |= x >> s;
-  return x + 1;
-}
-
 template <int BLOCK, class OpT, class Tin, class AccT>
 void launch_block(int kernel, const Tin* in, uint64_t n, AccT* dst, int blocks, hipStream_t s) {
   const size_t smem = static_cast<size_t>(BLOCK) * sizeof(AccT);
@@ -222,10 +216,10 @@ LadderPasses run(int kernel, const void* in, uint64_t n, void* out, void* scratc
 void ladder_geometry(int kernel, uint64_t n, int max_threads, int max_blocks, int* blocks, int* threads) {
   uint64_t t, b;
   if (kernel < 3) {
-    t = n < static_cast<uint64_t>(max_threads) ? ladder::next_pow2(n) : max_threads;
+    t = n < static_cast<uint64_t>(max_threads) ? next_pow2(n) : max_threads;
     b = (n + t - 1) / t;
   } else {
-    t = n < 2ull * max_threads ? ladder::next_pow2((n + 1) / 2) : max_threads;
+    t = n < 2ull * max_threads ? next_pow2((n + 1) / 2) : max_threads;
     b = (n + t * 2 - 1) / (t * 2);
   }
   if (t < 1) t = 1;  // (any power of two: sub-wave blocks reduce over their active lanes only)

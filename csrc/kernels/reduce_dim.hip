@@ -24,18 +24,14 @@
 #include "mireduce/half.hpp"
 #include "mireduce/ops.hpp"
 #include "mireduce/reduce_dim.hpp"
+#include "mireduce/row_layout.hpp"
 #include "mireduce/vec16.hpp"
+#include "row_stream.hpp"
 
 namespace mireduce {
 namespace kern {
 
-constexpr int kDimBlock = 256;
-constexpr int kRowUnroll = 8;  // vectors in flight per lane (8 KB per wave)
 constexpr int kColUnroll = 8;  // rows in flight per thread
-
-// 16 readable bytes: the load target of lanes that have nothing to load (branch-free issue).
-template <class V>
-__device__ V g_dummy_vec;
 
 struct RowArgs {
   const void* in;
@@ -54,11 +50,8 @@ struct RowArgs {
 // round) — fewer, wider concurrent streams than a wave per segment, as in reduce_many.hip.
 template <class OpT, class T, class AccT>
 __global__ __launch_bounds__(kDimBlock) void rows_kernel(RowArgs a) {
-  using V = typename Vec16<T>::type;
-  constexpr int N = Vec16<T>::N;
   constexpr int U = kRowUnroll;
-  constexpr int kWaves = kDimBlock / 64;
-  __shared__ AccT lds[kWaves];
+  __shared__ AccT lds[kDimBlock / 64];
   const int tid = threadIdx.x;
   const uint64_t nseg = a.rows * a.splits;
   const T* base = static_cast<const T*>(a.in);
@@ -70,56 +63,18 @@ __global__ __launch_bounds__(kDimBlock) void rows_kernel(RowArgs a) {
     const uint64_t b = (seg % a.splits) * a.seg_len;
     const uint64_t e = std::min<uint64_t>(a.cols, b + a.seg_len);
     const T* p = base + r * a.cols;
-    if (b < e) {
-      const uintptr_t addr = reinterpret_cast<uintptr_t>(p + b);
-      uint64_t head = addr % 16 ? (16 - addr % 16) / sizeof(T) : 0;
-      if (head > e - b) head = e - b;
-      if (static_cast<uint64_t>(tid) < head) acc[0] = OpT::apply(acc[0], OpT::pre(static_cast<AccT>(p[b + tid])));
-      const uint64_t vb = b + head;
-      const uint64_t nvec = (e - vb) / N;
-      const V* vp = reinterpret_cast<const V*>(p + vb);
-      uint64_t i = tid;
-      for (; i + static_cast<uint64_t>(U - 1) * kDimBlock < nvec; i += static_cast<uint64_t>(U) * kDimBlock) {
-        V v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(vp + i + static_cast<uint64_t>(u) * kDimBlock);
-        // all loads out before the first use: MIN/MAX's inline v_min/v_max otherwise made hipcc
-        // wait for each load in turn (one 16-byte load in flight per lane)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-          for (int k = 0; k < N; ++k) acc[u] = OpT::apply(acc[u], OpT::pre(elem<T, AccT>(v[u], k)));
-        }
-      }
-      for (; i < nvec; i += kDimBlock) {
-        const V v = __builtin_nontemporal_load(vp + i);
-#pragma unroll
-        for (int k = 0; k < N; ++k) acc[0] = OpT::apply(acc[0], OpT::pre(elem<T, AccT>(v, k)));
-      }
-      const uint64_t tb = vb + nvec * N;
-      if (static_cast<uint64_t>(tid) < e - tb) acc[1] = OpT::apply(acc[1], OpT::pre(static_cast<AccT>(p[tb + tid])));
-    }
+    if (b < e) stream_segment<OpT, T, AccT, kDimBlock, U>(p, b, e, acc, tid);
 #pragma unroll
     for (int u = 1; u < U; ++u) acc[0] = OpT::apply(acc[0], acc[u]);
-    AccT v = acc[0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = OpT::apply(v, __shfl_xor(v, off, 64));
-    if ((tid & 63) == 0) lds[tid >> 6] = v;
-    __syncthreads();
+    const AccT v = block_fold_thread0<OpT, AccT, kDimBlock>(acc[0], lds, tid);
     if (tid == 0) {
-#pragma unroll
-      for (int w = 1; w < kWaves; ++w) v = OpT::apply(v, lds[w]);
       AccT* out = static_cast<AccT*>(a.out);
       if (a.splits == 1) {
         out[r] = v;
       } else {
         AccT* part = static_cast<AccT*>(a.partials);
         store_sc1(&part[seg], v);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned prev = __hip_atomic_fetch_add(&a.tickets[r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (prev == a.splits - 1) {  // last segment of row r: fold in segment order
-          __hip_atomic_store(&a.tickets[r], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (take_ticket(a.tickets, r, a.splits)) {  // last segment of row r: fold in segment order
           AccT t = OpT::template identity<AccT>();
           for (uint64_t j = 0; j < a.splits; ++j) t = OpT::apply(t, load_sc1(&part[r * a.splits + j]));
           out[r] = t;
@@ -144,6 +99,7 @@ __global__ __launch_bounds__(kDimBlock) void short_rows_kernel(RowArgs a) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
   constexpr int U = kRowUnroll;
+  // own lane-group geometry, not lane_groups of row_stream.hpp: that moved hipcc's code in all 87 variants
   const int lane = threadIdx.x & 63;
   const int lpr = a.lpr;
   const int per_wave = 64 / lpr;
@@ -161,7 +117,7 @@ __global__ __launch_bounds__(kDimBlock) void short_rows_kernel(RowArgs a) {
       for (int j = 0; j < U; ++j) {
         const uint64_t r = row0 + static_cast<uint64_t>(j) * per_wave + sub;
         const bool ok = r < a.rows && static_cast<uint64_t>(sl) < vecs;
-        v[j] = __builtin_nontemporal_load(ok ? vbase + r * vecs + sl : &g_dummy_vec<V>);
+        v[j] = __builtin_nontemporal_load(ok ? vbase + r * vecs + sl : &dummy_vec<V>);
       }
     };
     auto fold = [&](uint64_t row0, const V* v) {
@@ -211,15 +167,13 @@ __global__ __launch_bounds__(kDimBlock) void short_rows_kernel(RowArgs a) {
       if constexpr (ALIGNED) {
         const uint64_t vecs = a.cols / N;
         has[j] = r < a.rows && static_cast<uint64_t>(sl) < vecs;
-        const V* src = has[j] ? reinterpret_cast<const V*>(base) + r * vecs + sl : &g_dummy_vec<V>;
+        const V* src = has[j] ? reinterpret_cast<const V*>(base) + r * vecs + sl : &dummy_vec<V>;
         v[j] = __builtin_nontemporal_load(src);
       } else {
         const T* p = base + r * a.cols;
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
-        uint64_t h = addr % 16 ? (16 - addr % 16) / sizeof(T) : 0;
-        if (h > a.cols) h = a.cols;
+        const uint64_t h = head_elems(p, 0, a.cols);
         has[j] = r < a.rows && static_cast<uint64_t>(sl) < (a.cols - h) / N;
-        const V* src = has[j] ? reinterpret_cast<const V*>(p + h) + sl : &g_dummy_vec<V>;
+        const V* src = has[j] ? reinterpret_cast<const V*>(p + h) + sl : &dummy_vec<V>;
         v[j] = __builtin_nontemporal_load(src);
       }
     }
@@ -234,9 +188,7 @@ __global__ __launch_bounds__(kDimBlock) void short_rows_kernel(RowArgs a) {
       }
       if (!ALIGNED && r < a.rows) {  // scalar head / tail (rows not 16-byte aligned, or lengths not a multiple of N)
         const T* p = base + r * a.cols;
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
-        uint64_t h = addr % 16 ? (16 - addr % 16) / sizeof(T) : 0;
-        if (h > a.cols) h = a.cols;
+        const uint64_t h = head_elems(p, 0, a.cols);
         for (uint64_t i = sl; i < h; i += lpr) acc = OpT::apply(acc, OpT::pre(static_cast<AccT>(p[i])));
         const uint64_t tb = h + (a.cols - h) / N * N;
         for (uint64_t i = tb + sl; i < a.cols; i += lpr) acc = OpT::apply(acc, OpT::pre(static_cast<AccT>(p[i])));
@@ -366,85 +318,7 @@ __global__ __launch_bounds__(kDimBlock) void cols_fold(const AccT* __restrict__ 
 // ----------------------------------------------------------------------------------------------
 namespace {
 
-constexpr uint64_t kMaxRowSplits = 1024;
-
-uint64_t next_pow2(uint64_t v) {
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-struct RowLayout {
-  int lpr;
-  uint64_t splits, seg_len, waves;
-  int grid;
-};
-
-constexpr int kMaxResident = 8;  // workgroups per CU assumed by the scratch-size bounds
-
-// Persistent grids are sized to what can be resident at once (a partial second round of
-// workgroups would leave most CUs idle at the end: 2048 column-kernel workgroups at 7 resident
-// per CU ran 15 % slower than a grid that fits).
-template <class K>
-int resident_per_cu(K kernel) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kern::kDimBlock, 0) != hipSuccess || n < 1) n = 1;
-  return std::min(n, kMaxResident);
-}
-
-RowLayout row_layout(size_t rows, size_t cols, DType t, int num_cus, int resident = kMaxResident) {
-  RowLayout L{};
-  const uint64_t N = 16 / dtype_size(t);
-  const uint64_t vecs = (cols + N - 1) / N;
-  const uint64_t target_waves = static_cast<uint64_t>(num_cus) * 16;
-  if (vecs <= 32) {  // short rows: a group of lpr lanes per row, 64/lpr rows per wave
-    L.lpr = static_cast<int>(next_pow2(std::max<uint64_t>(vecs, 1)));
-    L.splits = 1;
-  } else {
-    L.lpr = 64;  // long rows: a workgroup per segment (rows_kernel)
-    const uint64_t min_seg_vecs = static_cast<uint64_t>(kern::kDimBlock) * kern::kRowUnroll;  // one full round
-    const uint64_t by_len = std::max<uint64_t>(1, vecs / min_seg_vecs);
-    const uint64_t want = rows ? (target_waves + rows - 1) / rows : 1;
-    L.splits = std::max<uint64_t>(1, std::min({want, by_len, kMaxRowSplits}));
-  }
-  L.seg_len = ((cols + L.splits - 1) / L.splits + N - 1) / N * N;
-  uint64_t blocks;
-  if (L.lpr < 64) {  // short rows: rows per wave trip = (64 / lpr) x kRowUnroll, 4 waves per workgroup
-    const uint64_t per_wave = (64 / L.lpr) * kern::kRowUnroll;
-    L.waves = (rows + per_wave - 1) / per_wave;
-    blocks = (L.waves + 3) / 4;
-  } else {  // long rows: one workgroup per segment
-    L.waves = rows * L.splits * 4;
-    blocks = rows * L.splits;
-  }
-  L.grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(blocks, static_cast<uint64_t>(num_cus) * resident)));
-  return L;
-}
-
-struct ColLayout {
-  bool vec;
-  uint64_t threads, splits, rows_per_split;
-  int blocks, tpc;
-};
-
-ColLayout col_layout(const void* in, size_t outer, size_t rows, size_t cols, DType t, int num_cus,
-                     int resident = kMaxResident) {
-  ColLayout L{};
-  const size_t es = dtype_size(t);
-  const uint64_t N = 16 / es;
-  L.vec = reinterpret_cast<uintptr_t>(in) % 16 == 0 && (cols * es) % 16 == 0;
-  L.threads = L.vec ? cols / N : cols;
-  L.tpc = static_cast<int>(std::min<uint64_t>(kern::kDimBlock, next_pow2(std::max<uint64_t>(L.threads, 1))));
-  L.blocks = static_cast<int>((L.threads + L.tpc - 1) / L.tpc);
-  const uint64_t G = kern::kDimBlock / L.tpc;  // row groups share a workgroup's columns
-  const uint64_t target = static_cast<uint64_t>(num_cus) * resident;  // resident workgroups
-  const uint64_t all = static_cast<uint64_t>(L.blocks) * outer;
-  uint64_t splits = all ? target / all : 1;
-  splits = std::max<uint64_t>(1, std::min<uint64_t>({splits, (rows + 16 * G - 1) / (16 * G), 65535}));
-  L.rows_per_split = rows ? (rows + splits - 1) / splits : 1;
-  L.splits = rows ? (rows + L.rows_per_split - 1) / L.rows_per_split : 1;
-  return L;
-}
+using namespace layout;
 
 // Resident workgroups per CU the persistent grids are sized for. Measured (tools/dim_wg_sweep.sh,
 // profiles/r1_session3/reduce_dim/wg_sweep_bf16.txt, 4 GB bf16): column reductions stream best
@@ -519,16 +393,16 @@ void launch_fold(const void* partials, uint64_t splits, uint64_t cols, void* out
 
 template <class OpT, class T, class AccT>
 int rows_resident(bool short_rows) {
-  static const int s = std::min(resident_per_cu(kern::short_rows_kernel<OpT, T, AccT, false>),
-                                resident_per_cu(kern::short_rows_kernel<OpT, T, AccT, true, true>));
-  static const int l = resident_per_cu(kern::rows_kernel<OpT, T, AccT>);
+  static const int s = std::min(resident_workgroups(kern::short_rows_kernel<OpT, T, AccT, false>, kern::kDimBlock),
+                                resident_workgroups(kern::short_rows_kernel<OpT, T, AccT, true, true>, kern::kDimBlock));
+  static const int l = resident_workgroups(kern::rows_kernel<OpT, T, AccT>, kern::kDimBlock);
   return short_rows ? s : l;
 }
 
 template <class OpT, class T, class AccT>
 int cols_resident(bool vec) {
-  static const int v = resident_per_cu(kern::cols_kernel<OpT, T, AccT, true>);
-  static const int sc = resident_per_cu(kern::cols_kernel<OpT, T, AccT, false>);
+  static const int v = resident_workgroups(kern::cols_kernel<OpT, T, AccT, true>, kern::kDimBlock);
+  static const int sc = resident_workgroups(kern::cols_kernel<OpT, T, AccT, false>, kern::kDimBlock);
   return vec ? v : sc;
 }
 
@@ -560,28 +434,12 @@ DimEntry lookup(Op op, DType t, DType acc) {
 
 }  // namespace
 
-// Rows split only when rows < num_cus x 16 (row_layout's target_waves), so every split launch's
-// per-row tickets fit one fixed region at the start of the scratch; the partials always start
-// after it (a row-count-dependent boundary let a later, taller launch read an earlier launch's
-// partial bits as tickets — the kernels leave only the ticket words zero).
-size_t row_ticket_region_bytes(int num_cus) {
-  return (static_cast<size_t>(num_cus) * 16 * sizeof(unsigned) + 255) / 256 * 256;
-}
-
 size_t reduce_rows_scratch_bytes(size_t rows, size_t cols, DType t, int num_cus) {
-  const RowLayout L = row_layout(rows, cols, t, num_cus);
-  if (L.splits <= 1) return 0;
-  return row_ticket_region_bytes(num_cus) + rows * L.splits * 8;
+  return row_scratch_bytes(rows, cols, t, num_cus);
 }
 
 size_t reduce_cols_scratch_bytes(size_t outer, size_t rows, size_t cols, DType t, DType acc, int num_cus) {
-  // The bound covers both layouts, whatever the base's alignment turns out to be: the vector layout
-  // has fewer workgroups per slab (more row ranges fit the grid), the one-column layout fewer row
-  // groups per workgroup (more row ranges fit the rows: a misaligned [8192, 128] bf16 slab is cut into
-  // 256 ranges where the vector layout's 32 were reserved, and [257, 64] into 5 where none was).
-  const ColLayout v = col_layout(nullptr, outer, rows, cols, t, num_cus);
-  const ColLayout s = col_layout(reinterpret_cast<const void*>(uintptr_t{1}), outer, rows, cols, t, num_cus);
-  const uint64_t splits = std::max(v.splits, s.splits);
+  const uint64_t splits = col_splits_bound(outer, rows, cols, t, num_cus);
   return splits > 1 ? splits * outer * cols * dtype_size(acc) : 0;
 }
 

@@ -22,6 +22,7 @@
 #include "mireduce/ops.hpp"
 #include "mireduce/reduce_many.hpp"
 #include "mireduce/vec16.hpp"
+#include "row_stream.hpp"
 
 namespace mireduce {
 namespace kern {
@@ -51,11 +52,8 @@ struct ManyArgs {
 
 template <class OpT, class T, class AccT>
 __global__ __launch_bounds__(kManyBlock) void many_kernel(ManyArgs a) {
-  using V = typename Vec16<T>::type;
-  constexpr int N = Vec16<T>::N;
   constexpr int U = kManyUnroll;
-  constexpr int kWaves = kManyBlock / 64;
-  __shared__ AccT lds[kWaves];
+  __shared__ AccT lds[kManyBlock / 64];
   __shared__ int last;
   const int tid = threadIdx.x;
   // A workgroup streams one segment at a time (its 256 lanes read 4 KB contiguous per load
@@ -67,43 +65,12 @@ __global__ __launch_bounds__(kManyBlock) void many_kernel(ManyArgs a) {
     AccT acc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[u] = OpT::template identity<AccT>();
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(p + g.begin);
-    uint64_t head = addr % 16 ? (16 - addr % 16) / sizeof(T) : 0;
-    if (head > g.end - g.begin) head = g.end - g.begin;
-    if (static_cast<uint64_t>(tid) < head) acc[0] = OpT::apply(acc[0], OpT::pre(static_cast<AccT>(p[g.begin + tid])));
-    const uint64_t vb = g.begin + head;
-    const uint64_t nvec = (g.end - vb) / N;
-    const V* vp = reinterpret_cast<const V*>(p + vb);
-    uint64_t i = tid;
-    for (; i + (U - 1) * kManyBlock < nvec; i += U * kManyBlock) {
-      V v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(vp + i + u * kManyBlock);
-      __builtin_amdgcn_sched_barrier(0);  // all loads out before the first use
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) acc[u] = OpT::apply(acc[u], OpT::pre(elem<T, AccT>(v[u], k)));
-      }
-    }
-    for (; i < nvec; i += kManyBlock) {
-      const V v = __builtin_nontemporal_load(vp + i);
-#pragma unroll
-      for (int k = 0; k < N; ++k) acc[0] = OpT::apply(acc[0], OpT::pre(elem<T, AccT>(v, k)));
-    }
-    const uint64_t tb = vb + nvec * N;
-    if (static_cast<uint64_t>(tid) < g.end - tb) acc[1] = OpT::apply(acc[1], OpT::pre(static_cast<AccT>(p[tb + tid])));
+    stream_segment<OpT, T, AccT, kManyBlock, U>(p, g.begin, g.end, acc, tid);
 #pragma unroll
     for (int u = 1; u < U; ++u) acc[0] = OpT::apply(acc[0], acc[u]);
-    AccT v = acc[0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = OpT::apply(v, __shfl_xor(v, off, 64));
-    if ((tid & 63) == 0) lds[tid >> 6] = v;
-    __syncthreads();
+    const AccT v = block_fold_thread0<OpT, AccT, kManyBlock>(acc[0], lds, tid);
     const TensorInfo ti = a.info[g.tensor];
     if (tid == 0) {
-#pragma unroll
-      for (int w = 1; w < kWaves; ++w) v = OpT::apply(v, lds[w]);
       AccT* out = static_cast<AccT*>(a.out);
       if (ti.nseg == 1) {
         out[g.tensor] = v;
@@ -111,10 +78,7 @@ __global__ __launch_bounds__(kManyBlock) void many_kernel(ManyArgs a) {
       } else {
         AccT* part = static_cast<AccT*>(a.partials);
         store_sc1(&part[s], v);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned prev = __hip_atomic_fetch_add(&a.tickets[g.tensor], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == ti.nseg - 1;
-        if (last) __hip_atomic_store(&a.tickets[g.tensor], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = take_ticket(a.tickets, g.tensor, ti.nseg);
       }
     }
     __syncthreads();
@@ -123,15 +87,8 @@ __global__ __launch_bounds__(kManyBlock) void many_kernel(ManyArgs a) {
       const AccT* part = static_cast<const AccT*>(a.partials) + ti.first_seg;
       AccT t = OpT::template identity<AccT>();
       for (uint32_t j = tid; j < ti.nseg; j += kManyBlock) t = OpT::apply(t, load_sc1(&part[j]));
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) t = OpT::apply(t, __shfl_xor(t, off, 64));
-      if ((tid & 63) == 0) lds[tid >> 6] = t;
-      __syncthreads();
-      if (tid == 0) {
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) t = OpT::apply(t, lds[w]);
-        static_cast<AccT*>(a.out)[g.tensor] = t;
-      }
+      t = block_fold_thread0<OpT, AccT, kManyBlock>(t, lds, tid);
+      if (tid == 0) static_cast<AccT*>(a.out)[g.tensor] = t;
     }
     __syncthreads();  // lds is rewritten by the next segment
   }
@@ -151,13 +108,7 @@ void launch_many(const kern::ManyArgs& a, int grid, hipStream_t s) {
 
 template <class OpT, class T, class AccT>
 int many_resident() {
-  static const int n = [] {
-    int r = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, kern::many_kernel<OpT, T, AccT>, kern::kManyBlock, 0) !=
-            hipSuccess || r < 1)
-      r = 1;
-    return std::min(r, 8);
-  }();
+  static const int n = resident_workgroups(kern::many_kernel<OpT, T, AccT>, kern::kManyBlock);
   return n;
 }
 

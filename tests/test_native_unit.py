@@ -48,6 +48,16 @@ def test_host_sanitizers():
         assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
+def test_rows_unit_plain_and_sanitized():
+    # the planners of reduce_dim / arg_reduce (mireduce/row_layout.hpp): scratch bounds, ticket regions, grids
+    r = run([os.path.join(BIN, "rows_unit")])
+    assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout + r.stderr
+    subprocess.run(["make", "-C", ROOT, "asan"], check=True, stdout=subprocess.DEVNULL)
+    r = run([os.path.join(ROOT, "build", "asan", "rows_unit")], env={"ASAN_OPTIONS": "detect_leaks=1"})
+    assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout + r.stderr
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
 def test_experiment_tools_build():
     # tools/window_ab.hip, dyntail_ab.hip and i32sum_ab.hip include the production kernel header directly
     # (their A/Bs run the real kern::reduce_stream): they must keep compiling as it changes.

@@ -108,6 +108,42 @@ def test_split_rows_are_deterministic_and_reusable():
 
 
 @pytest.mark.gpu
+def test_device_split_scratch_reuse_with_more_rows():
+    """A split launch with few rows and many segments followed, on the same stream and scratch, by a split
+    launch with MORE rows must not read the first launch's partials as its tickets (the twin of the test of
+    the same name in test_arg_reduce.py: the ticket region of the scratch is fixed, not sized by the rows)."""
+    from cuda_mpi_reductions_amd._native import native
+    import sys
+    rd = sys.modules[reduce_dim.__module__]  # ops/reduce_dim.py, which keeps the scratch buffers
+    from cuda_mpi_reductions_amd.ops.reduce import dtype_code
+    C = native()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    f64 = dtype_code(torch.float64)
+    few = (2, 4_000_037)
+    need_few = C.reduce_rows_scratch_bytes(few[0], few[1], f64, ncu)
+    assert need_few > 0, "the first shape must split its rows on this device"  # scratch <=> splits > 1
+    # More rows, still split, and no more scratch than the first, so the Python layer reuses the buffer.
+    # More than 64 rows: a ticket region sized by the row count (rows x 4 bytes rounded up to 256) would
+    # then end at 256 bytes for the first launch and beyond it for the second, whose tickets 64.. would
+    # lie where the first launch left partials.
+    more = next((s for s in [(128, 16_384), (256, 16_384), (96, 16_384), (80, 32_768)]
+                 if 0 < C.reduce_rows_scratch_bytes(s[0], s[1], f64, ncu) <= need_few), None)
+    assert more is not None and more[0] > 64, (ncu, need_few)
+    x1 = _make(few, torch.float64, seed=11)
+    x2 = _make(more, torch.float64, seed=12)
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, "rows")
+    _check(reduce_dim(x1, "sum", 1), x1, "sum", 1)
+    buf = rd._scratch[key].data_ptr()
+    for _ in range(3):
+        _check(reduce_dim(x2, "sum", 1), x2, "sum", 1)
+        _check(reduce_dim(x1, "max", 1), x1, "max", 1)
+        _check(reduce_dim(x2, "min", 1), x2, "min", 1)
+        _check(reduce_dim(x1, "sum", 1), x1, "sum", 1)
+    assert rd._scratch[key].data_ptr() == buf  # one buffer served every launch
+
+
+@pytest.mark.gpu
 def test_nan_and_keepdim_and_out():
     x = torch.zeros(4, 1000, dtype=torch.float32, device="cuda")
     x[2, 500] = float("nan")
