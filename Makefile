@@ -171,7 +171,7 @@ $(BUILD)/bin/cpp_consumer: examples/cpp_consumer/main.cpp $(SHLIB) $(HEADERS)
 # kernels read untrusted input (tests/native/<name>_unit.cpp plus the runtime sources listed here).
 # (the units whose tests/native source is in the tree: the library, extension and apps also build from a tree
 # that ships without all of the native test sources)
-FEATURE_UNITS := $(foreach u,scan segment histogram sort topk select segscan rows,$(if $(wildcard tests/native/$(u)_unit.cpp),$(u)))
+FEATURE_UNITS := $(foreach u,scan segment histogram sort topk select segscan rows softmax,$(if $(wildcard tests/native/$(u)_unit.cpp),$(u)))
 UNIT_SRCS_scan      := csrc/runtime/scan_cpu.cpp
 UNIT_SRCS_segment   := csrc/runtime/segment_cpu.cpp
 UNIT_SRCS_histogram := csrc/runtime/histogram_cpu.cpp
@@ -180,6 +180,7 @@ UNIT_SRCS_topk      := csrc/runtime/topk_cpu.cpp
 UNIT_SRCS_select    := csrc/runtime/select_cpu.cpp
 UNIT_SRCS_segscan   := csrc/runtime/segscan_cpu.cpp csrc/runtime/segment_cpu.cpp
 UNIT_SRCS_rows      :=
+UNIT_SRCS_softmax   := csrc/runtime/softmax_cpu.cpp
 UNIT_SRCS_host      := $(filter-out csrc/apps/reduce_mpi.cpp,$(MPI_SRCS)) csrc/runtime/peer_access.cpp
 UNIT_FLAGS_host     := -Icsrc/include -I$(BUILD)/gen -DMIREDUCE_NO_HIP
 UNIT_FLAGS_feature  := -Icsrc/include -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -DMIREDUCE_NO_HIP

@@ -30,6 +30,7 @@
 #include "mireduce/segscan.hpp"
 #include "mireduce/sort.hpp"
 #include "mireduce/select.hpp"
+#include "mireduce/softmax.hpp"
 #include "mireduce/topk.hpp"
 #include "mireduce/trace.hpp"
 #include "mireduce/types.hpp"
@@ -982,6 +983,96 @@ PYBIND11_MODULE(_C, m) {
         return topk_temp_bytes(rows, cols, k, static_cast<DType>(dtype));
       },
       py::arg("rows"), py::arg("cols"), py::arg("k"), py::arg("dtype"));
+  // Softmax / log-softmax / logsumexp / cross-entropy (csrc/kernels/softmax.hip, csrc/runtime/softmax_cpu.cpp).
+  auto softmax_plan_dict = [](const SoftmaxPlan& p) {
+    py::dict d;
+    d["variant"] = p.variant;
+    d["grid"] = p.grid;
+    d["block"] = p.block;
+    d["lanes_per_row"] = p.lanes_per_row;
+    d["rows_per_wg"] = p.rows_per_wg;
+    d["items_per_lane"] = p.items_per_lane;
+    d["splits"] = p.splits;
+    d["chunk_elems"] = p.chunk_elems;
+    d["tile_elems"] = p.tile_elems;
+    d["reads"] = p.reads;
+    d["launches"] = p.launches;
+    d["temp_bytes"] = p.temp_bytes;
+    d["wave_max_cols"] = kSoftmaxWaveMaxCols;
+    d["resident_cols"] = kSoftmaxResidentCols;
+    d["max_splits"] = kSoftmaxMaxSplits;
+    return d;
+  };
+  auto softmax_cfg = [](int variant, int splits, int max_blocks, int wg_per_cu, int lanes_per_row) {
+    SoftmaxConfig cfg;
+    cfg.variant = variant;
+    cfg.splits = splits;
+    cfg.max_blocks = max_blocks;
+    cfg.wg_per_cu = wg_per_cu;
+    cfg.lanes_per_row = lanes_per_row;
+    return cfg;
+  };
+  auto softmax_mode = [](int mode, int dtype, int out_dtype) {
+    MIREDUCE_REQUIRE(mode >= 0 && mode < kNumSoftmaxModes, "softmax mode out of range");
+    MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes && out_dtype >= 0 && out_dtype < kNumDTypes, "dtype out of range");
+    return static_cast<SoftmaxMode>(mode);
+  };
+  auto softmax_outputs = [](uintptr_t out, int out_dtype, uintptr_t max, uintptr_t sumexp, uintptr_t lse, uintptr_t loss,
+                            uintptr_t target) {
+    SoftmaxOutputs o;
+    o.out = as_ptr<void>(out);
+    o.out_t = static_cast<DType>(out_dtype);
+    o.max = as_ptr<void>(max);
+    o.sumexp = as_ptr<void>(sumexp);
+    o.lse = as_ptr<void>(lse);
+    o.loss = as_ptr<void>(loss);
+    o.target = as_ptr<const int64_t>(target);
+    return o;
+  };
+  m.def(
+      "softmax",
+      [softmax_plan_dict, softmax_cfg, softmax_mode, softmax_outputs](int mode, uintptr_t in, uint64_t rows, uint64_t cols, int dtype,
+                                                                      double scale, uintptr_t out, int out_dtype, uintptr_t max,
+                                                                      uintptr_t sumexp, uintptr_t lse, uintptr_t loss, uintptr_t target,
+                                                                      uintptr_t temp, uint64_t temp_bytes, uintptr_t stream, int variant,
+                                                                      int splits, int max_blocks, int wg_per_cu, int lanes_per_row) {
+        const SoftmaxMode sm = softmax_mode(mode, dtype, out_dtype);
+        return softmax_plan_dict(softmax(sm, as_ptr<const void>(in), rows, cols, static_cast<DType>(dtype), scale,
+                                         softmax_outputs(out, out_dtype, max, sumexp, lse, loss, target), as_ptr<void>(temp), temp_bytes,
+                                         as_stream(stream), softmax_cfg(variant, splits, max_blocks, wg_per_cu, lanes_per_row)));
+      },
+      py::arg("mode"), py::arg("in_ptr"), py::arg("rows"), py::arg("cols"), py::arg("dtype"), py::arg("scale"), py::arg("out_ptr"),
+      py::arg("out_dtype"), py::arg("max_ptr"), py::arg("sumexp_ptr"), py::arg("lse_ptr"), py::arg("loss_ptr"), py::arg("target_ptr"),
+      py::arg("temp_ptr"), py::arg("temp_bytes"), py::arg("stream") = 0, py::arg("variant") = 0, py::arg("splits") = 0,
+      py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0, py::arg("lanes_per_row") = 0);
+  m.def(
+      "cpu_softmax",
+      [softmax_mode, softmax_outputs](int mode, uintptr_t in, uint64_t rows, uint64_t cols, int dtype, double scale, uintptr_t out,
+                                      int out_dtype, uintptr_t max, uintptr_t sumexp, uintptr_t lse, uintptr_t loss, uintptr_t target) {
+        const SoftmaxMode sm = softmax_mode(mode, dtype, out_dtype);
+        const SoftmaxOutputs o = softmax_outputs(out, out_dtype, max, sumexp, lse, loss, target);
+        py::gil_scoped_release nogil;
+        cpu_softmax(sm, as_ptr<const void>(in), rows, cols, static_cast<DType>(dtype), scale, o);
+      },
+      py::arg("mode"), py::arg("in_ptr"), py::arg("rows"), py::arg("cols"), py::arg("dtype"), py::arg("scale"), py::arg("out_ptr"),
+      py::arg("out_dtype"), py::arg("max_ptr"), py::arg("sumexp_ptr"), py::arg("lse_ptr"), py::arg("loss_ptr"), py::arg("target_ptr"));
+  m.def(
+      "softmax_plan",
+      [softmax_plan_dict, softmax_cfg, softmax_mode](int mode, uint64_t rows, uint64_t cols, int dtype, int num_cus, int variant, int splits,
+                                                     int max_blocks, int wg_per_cu, int lanes_per_row) {
+        const SoftmaxMode sm = softmax_mode(mode, dtype, dtype);
+        return softmax_plan_dict(plan_softmax(rows, cols, static_cast<DType>(dtype), sm,
+                                              softmax_cfg(variant, splits, max_blocks, wg_per_cu, lanes_per_row), num_cus));
+      },
+      py::arg("mode"), py::arg("rows"), py::arg("cols"), py::arg("dtype"), py::arg("num_cus") = 256, py::arg("variant") = 0,
+      py::arg("splits") = 0, py::arg("max_blocks") = 0, py::arg("wg_per_cu") = 0, py::arg("lanes_per_row") = 0);
+  m.def(
+      "softmax_temp_bytes",
+      [](uint64_t rows, uint64_t cols, int dtype) {
+        MIREDUCE_REQUIRE(dtype >= 0 && dtype < kNumDTypes, "dtype out of range");
+        return softmax_temp_bytes(rows, cols, static_cast<DType>(dtype));
+      },
+      py::arg("rows"), py::arg("cols"), py::arg("dtype"));
   // Stream compaction (csrc/kernels/select.hip, csrc/runtime/select_cpu.cpp).
   auto select_plan_dict = [](const SelectPlan& p) {
     py::dict d;

@@ -16,3 +16,4 @@ from .histogram import HistogramConfig, bincount, histc, histogram_plan  # noqa:
 from .sort import SortConfig, argsort, group_by_key, sort, sort_plan  # noqa: F401
 from .topk import TopkConfig, topk, topk_plan  # noqa: F401
 from .select import SelectConfig, masked_select, nonzero, select_plan, unique, unique_consecutive  # noqa: F401
+from .softmax import SoftmaxConfig, cross_entropy, log_softmax, logsumexp, softmax, softmax_plan  # noqa: F401
