@@ -54,7 +54,21 @@ struct SumSqOp {
 // On the device the instructions are emitted directly: llvm.minnum in IEEE mode makes hipcc
 // canonicalise every operand first (an extra `v_max_f64 x, x, x` per element, which doubled the
 // VALU work of the MIN/MAX streaming loop). The hardware ops already return the non-NaN operand
-// for quiet NaNs; only signalling-NaN inputs (never produced by arithmetic) would differ.
+// for quiet NaNs. A signalling NaN is another matter while the wave's IEEE mode bit is set (the
+// default of a compute kernel): v_min / v_max then return the QUIETED NaN, whatever the other
+// operand holds, so an accumulator loses everything it had gathered (the next combine ignores the
+// NaN: a wrong number, not a NaN) and a chain that ends on it gives NaN. Memory can hold such
+// patterns (uninitialised or bit-cast data). With the bit clear the instructions treat both kinds
+// of NaN alike, which is the documented rule, so every kernel that takes MIN / MAX of raw input
+// starts with minmax_ignore_all_nans(): one scalar instruction per wave, nothing per element.
+// The bit only changes how signalling NaNs are handled; sums still come out NaN.
+#if defined(__HIPCC__)
+__device__ __forceinline__ void minmax_ignore_all_nans() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 9, 1), 0");  // MODE.IEEE = 0, this wave only
+#endif
+}
+#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ double hw_min(double a, double b) {
   double r;

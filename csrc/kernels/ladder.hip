@@ -42,13 +42,22 @@ __device__ __forceinline__ AccT* lds_array() {
   return reinterpret_cast<AccT*>(smem_raw);
 }
 
+// The first element of a thread's chain enters through the op like every later one: a block of one
+// thread combines it with nothing else, and a NaN must still give the identity (float MIN / MAX).
+template <class OpT, class AccT, class Tin>
+__device__ __forceinline__ AccT first(const Tin* __restrict__ in, uint64_t i, uint64_t n) {
+  const AccT id = OpT::template identity<AccT>();
+  return i < n ? OpT::apply(id, static_cast<AccT>(in[i])) : id;
+}
+
 // k0..k2: one element per thread, LDS tree over the whole block.
 template <int K, class OpT, class Tin, class AccT>
 __global__ void k012(const Tin* __restrict__ in, uint64_t n, AccT* __restrict__ out) {
   AccT* sdata = lds_array<AccT>();
+  minmax_ignore_all_nans();
   const unsigned tid = threadIdx.x;
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + tid;
-  sdata[tid] = i < n ? static_cast<AccT>(in[i]) : OpT::template identity<AccT>();
+  sdata[tid] = first<OpT, AccT>(in, i, n);
   __syncthreads();
   if constexpr (K == 0) {
     for (unsigned s = 1; s < blockDim.x; s *= 2) {
@@ -74,9 +83,10 @@ __global__ void k012(const Tin* __restrict__ in, uint64_t n, AccT* __restrict__ 
 template <int K, class OpT, class Tin, class AccT>
 __global__ void k34(const Tin* __restrict__ in, uint64_t n, AccT* __restrict__ out) {
   AccT* sdata = lds_array<AccT>();
+  minmax_ignore_all_nans();
   const unsigned tid = threadIdx.x;
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (blockDim.x * 2) + tid;
-  AccT v = i < n ? static_cast<AccT>(in[i]) : OpT::template identity<AccT>();
+  AccT v = first<OpT, AccT>(in, i, n);
   if (i + blockDim.x < n) v = OpT::apply(v, static_cast<AccT>(in[i + blockDim.x]));
   sdata[tid] = v;
   __syncthreads();
@@ -117,9 +127,10 @@ __device__ __forceinline__ void unrolled_tail(AccT* sdata, AccT v, AccT* out) {
 template <int BLOCK, class OpT, class Tin, class AccT>
 __global__ __launch_bounds__(BLOCK) void k5(const Tin* __restrict__ in, uint64_t n, AccT* __restrict__ out) {
   AccT* sdata = lds_array<AccT>();
+  minmax_ignore_all_nans();
   const unsigned tid = threadIdx.x;
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (BLOCK * 2) + tid;
-  AccT v = i < n ? static_cast<AccT>(in[i]) : OpT::template identity<AccT>();
+  AccT v = first<OpT, AccT>(in, i, n);
   if (i + BLOCK < n) v = OpT::apply(v, static_cast<AccT>(in[i + BLOCK]));
   sdata[tid] = v;
   __syncthreads();
@@ -129,6 +140,7 @@ __global__ __launch_bounds__(BLOCK) void k5(const Tin* __restrict__ in, uint64_t
 template <int BLOCK, class OpT, class Tin, class AccT>
 __global__ __launch_bounds__(BLOCK) void k6(const Tin* __restrict__ in, uint64_t n, AccT* __restrict__ out) {
   AccT* sdata = lds_array<AccT>();
+  minmax_ignore_all_nans();
   const unsigned tid = threadIdx.x;
   uint64_t i = static_cast<uint64_t>(blockIdx.x) * (BLOCK * 2) + tid;
   const uint64_t grid_size = static_cast<uint64_t>(BLOCK) * 2 * gridDim.x;

@@ -49,9 +49,12 @@ __device__ __forceinline__ Mom block_mom(Mom v, Mom* lds) {
   return v;
 }
 
+// The shift K: x[0], or 0 when x[0] is not finite (x - inf is NaN for x = inf, which would turn an
+// infinite mean into NaN; a NaN shift would poison every term). Both kernels derive it the same way.
 template <class T>
 __device__ __forceinline__ double first_value(const void* p) {
-  return static_cast<double>(*static_cast<const T*>(p));
+  const double k = static_cast<double>(*static_cast<const T*>(p));
+  return k - k == 0.0 ? k : 0.0;
 }
 
 // One element: shifted Σ and Σ² in fp64; MIN/MAX in the narrowest exact type E (fp32 for fp32 /
@@ -72,7 +75,8 @@ __global__ __launch_bounds__(BLOCK) void moments_stream(const T* __restrict__ in
   using E = std::conditional_t<std::is_same_v<T, double>, double, float>;
   constexpr int N = Vec16<T>::N;
   __shared__ Mom lds[BLOCK / 64];
-  const double K = n ? static_cast<double>(in[0]) : 0.0;
+  minmax_ignore_all_nans();
+  const double K = n ? first_value<T>(in) : 0.0;
   double s[UNROLL], q[UNROLL];
   E mn[UNROLL], mx[UNROLL];
 #pragma unroll
@@ -119,6 +123,7 @@ __global__ __launch_bounds__(256) void moments_finalize(const Mom* __restrict__ 
                                                         const void* __restrict__ first, uint64_t n,
                                                         double* __restrict__ out) {
   __shared__ Mom lds[4];
+  minmax_ignore_all_nans();
   Mom m{0.0, 0.0, MinOp::identity<double>(), MaxOp::identity<double>()};
   for (int i = threadIdx.x; i < count; i += 256) m = mom_combine(m, partials[i]);
   m = block_mom<256>(m, lds);

@@ -52,6 +52,7 @@ template <class OpT, class T, class AccT>
 __global__ __launch_bounds__(kDimBlock) void rows_kernel(RowArgs a) {
   constexpr int U = kRowUnroll;
   __shared__ AccT lds[kDimBlock / 64];
+  minmax_ignore_all_nans();
   const int tid = threadIdx.x;
   const uint64_t nseg = a.rows * a.splits;
   const T* base = static_cast<const T*>(a.in);
@@ -99,6 +100,7 @@ __global__ __launch_bounds__(kDimBlock) void short_rows_kernel(RowArgs a) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
   constexpr int U = kRowUnroll;
+  minmax_ignore_all_nans();
   // own lane-group geometry, not lane_groups of row_stream.hpp: that moved hipcc's code in all 87 variants
   const int lane = threadIdx.x & 63;
   const int lpr = a.lpr;
@@ -218,6 +220,7 @@ __global__ __launch_bounds__(kDimBlock) void cols_kernel(ColArgs a) {
   using V = typename Vec16<T>::type;
   constexpr int N = VEC ? Vec16<T>::N : 1;
   __shared__ AccT lds[kDimBlock * N];
+  minmax_ignore_all_nans();
   const int tpc = a.tpc;
   const int G = kDimBlock / tpc;
   const int g = threadIdx.x / tpc, tc = threadIdx.x % tpc;
@@ -293,6 +296,7 @@ template <class OpT, class AccT>
 __global__ __launch_bounds__(kDimBlock) void cols_fold(const AccT* __restrict__ partials, uint64_t splits,
                                                        uint64_t cols, int ct, AccT* __restrict__ out) {
   __shared__ AccT lds[kDimBlock];
+  minmax_ignore_all_nans();
   const int SG = kDimBlock / ct;
   const int g = threadIdx.x / ct, tc = threadIdx.x % ct;
   const uint64_t c = static_cast<uint64_t>(blockIdx.x) * ct + tc;

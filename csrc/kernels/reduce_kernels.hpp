@@ -535,6 +535,7 @@ __global__ __launch_bounds__(BLOCK) void reduce_stream(Args a) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
   __shared__ AccT lds[BLOCK / 64];
+  minmax_ignore_all_nans();
 
   AccT acc[UNROLL];
 #pragma unroll
@@ -767,6 +768,7 @@ __global__ __launch_bounds__(256) void finalize(const AccT* __restrict__ partial
                                                 AccT* __restrict__ out, unsigned* fan, uint64_t* slots,
                                                 unsigned fan_slots) {
   __shared__ AccT lds[4];
+  minmax_ignore_all_nans();
   AccT s = OpT::template identity<AccT>();
   for (uint64_t i = threadIdx.x; i < count; i += 256) s = OpT::apply(s, partials[i]);
   s = block_reduce<OpT, AccT, 256>(s, lds);
@@ -786,11 +788,22 @@ __global__ __launch_bounds__(256) void finalize(const AccT* __restrict__ partial
   }
 }
 
+// a op b of the element-wise combine. Float MIN / MAX start from the identity, so that a NaN in both
+// operands gives the identity, as a reduction over only NaNs does (minNum(NaN, NaN) alone is NaN).
+template <class OpT, class T>
+__device__ __forceinline__ T combine_pair(T a, T b) {
+  if constexpr (std::is_floating_point_v<T> && (std::is_same_v<OpT, MinOp> || std::is_same_v<OpT, MaxOp>))
+    return OpT::apply(OpT::apply(OpT::template identity<T>(), a), b);
+  else
+    return OpT::apply(a, b);
+}
+
 template <class OpT, class T>
 __global__ __launch_bounds__(256) void combine(T* __restrict__ inout, const T* __restrict__ other,
                                                uint64_t n) {
   using V = typename Vec16<T>::type;
   constexpr int N = Vec16<T>::N;
+  minmax_ignore_all_nans();
   const uint64_t nvec = n / N;
   V* vio = reinterpret_cast<V*>(inout);
   const V* vo = reinterpret_cast<const V*>(other);
@@ -799,13 +812,13 @@ __global__ __launch_bounds__(256) void combine(T* __restrict__ inout, const T* _
     V x = __builtin_nontemporal_load(vio + i);
     const V y = __builtin_nontemporal_load(vo + i);
 #pragma unroll
-    for (int k = 0; k < N; ++k) x[k] = OpT::apply(x[k], y[k]);
+    for (int k = 0; k < N; ++k) x[k] = combine_pair<OpT>(x[k], y[k]);
     __builtin_nontemporal_store(x, vio + i);
   }
   const uint64_t rem = n - nvec * N;
   if (blockIdx.x == 0 && threadIdx.x < rem) {
     const uint64_t i = nvec * N + threadIdx.x;
-    inout[i] = OpT::apply(inout[i], other[i]);
+    inout[i] = combine_pair<OpT>(inout[i], other[i]);
   }
 }
 

@@ -55,6 +55,7 @@ __global__ __launch_bounds__(kManyBlock) void many_kernel(ManyArgs a) {
   constexpr int U = kManyUnroll;
   __shared__ AccT lds[kManyBlock / 64];
   __shared__ int last;
+  minmax_ignore_all_nans();
   const int tid = threadIdx.x;
   // A workgroup streams one segment at a time (its 256 lanes read 4 KB contiguous per load
   // round): fewer, wider concurrent streams than a wave per segment (13 GB bf16 parameter list:

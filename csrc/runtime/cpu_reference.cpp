@@ -27,7 +27,8 @@ struct Compensated {
     else c += (x - t) + sum;
     sum = t;
   }
-  A value() const { return sum + c; }
+  // Once the sum is infinite (or NaN) the compensation term is inf - inf = NaN: the sum alone is the answer.
+  A value() const { return std::isfinite(sum) ? sum + c : sum; }
 };
 
 // Floating sums are compensated in fp64 whatever the accumulator type (per-thread partials stay

@@ -2,7 +2,8 @@
 (fp32 / fp64 / bf16 / fp16 storage; all statistics are computed in fp64).
 
 Device tensors: one streaming HIP pass (csrc/kernels/moments.hip) computing Σ(x-K), Σ(x-K)²,
-min and max with K = x[0] (shifted-data variance), then a one-workgroup fold. Pattern reference:
+min and max with K = x[0] (shifted-data variance; K = 0 when x[0] is not finite), then a one-workgroup fold.
+min and max ignore NaN; count, mean and var are NaN as soon as a NaN is present. Pattern reference:
 the fused Σx/Σx² reduction of the vendored MonteCarlo sample (MonteCarlo_reduction.cuh:20-63).
 Across ranks (``moments(x, group=...)``) the per-rank raw moments are combined exactly with the
 pairwise (Chan et al.) update after an all-gather of 4 values per rank.
@@ -38,9 +39,13 @@ def _raw(x: torch.Tensor):
     else:
         xd = x.double()
         k = float(xd[0])
+        if not math.isfinite(k):  # inf - inf would poison the mean; a NaN first element must not shift either
+            k = 0.0
         d = xd - k
         s, q = float(d.sum()), float((d * d).sum())
-        mn, mx = float(xd.min()), float(xd.max())
+        nan = xd.isnan()  # min / max ignore NaN, as the kernel's MinOp / MaxOp do
+        mn = float(torch.where(nan, torch.full_like(xd, math.inf), xd).min())
+        mx = float(torch.where(nan, torch.full_like(xd, -math.inf), xd).max())
     mean = k + s / n
     m2 = max(q - s * s / n, 0.0)
     return n, mean, m2, mn, mx
