@@ -62,6 +62,8 @@ struct SumSqOp {
 // of NaN alike, which is the documented rule, so every kernel that takes MIN / MAX of raw input
 // starts with minmax_ignore_all_nans(): one scalar instruction per wave, nothing per element.
 // The bit only changes how signalling NaNs are handled; sums still come out NaN.
+// (Not free everywhere: the segmented kernels measured 7 to 23 % slower with it, profiles/scan_special/, so
+// scan.hip, segscan.hip and segment.hip call it in their float MIN / MAX / AMAX instantiations only.)
 #if defined(__HIPCC__)
 __device__ __forceinline__ void minmax_ignore_all_nans() {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -123,6 +125,14 @@ struct MaxOp {
   }
   template <class T> MIREDUCE_HD static T pre(T x) { return x; }
 };
+
+// Whether a kernel instantiated for (OpT, AccT) takes a float MIN / MAX of raw input (AMAX combines through
+// MaxOp): the kernels whose other instantiations must keep their code call minmax_ignore_all_nans() under it.
+struct AbsMaxOp;
+template <class OpT, class AccT>
+inline constexpr bool kFloatMinMax =
+    std::is_floating_point_v<AccT> &&
+    (std::is_same_v<OpT, MinOp> || std::is_same_v<OpT, MaxOp> || std::is_same_v<OpT, AbsMaxOp>);
 
 // max |x| (the amax of FP8 scaling, the inf-norm): |x| on load, MAX to combine (identity 0 since
 // every transformed value is >= 0; a NaN input is ignored like in MaxOp). Floating types only.

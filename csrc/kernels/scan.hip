@@ -188,6 +188,7 @@ __global__ void scan_empty(ScanArgs a) {
 template <class OpT, class T, class AccT>
 __global__ __launch_bounds__(kScanBlock) void scan_chunk_totals(ScanArgs a) {
   __shared__ AccT lds[kScanWaves];
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   uint64_t t0, t1;
   chunk_tiles(a.tiles_per_wg, a.ntiles, t0, t1);
   AccT acc = OpT::template identity<AccT>();
@@ -207,6 +208,7 @@ template <class OpT, class T, class AccT, class OutT>
 __global__ __launch_bounds__(kScanBlock) void scan_chunks(ScanArgs a) {
   __shared__ AccT lds[kScanRows];
   __shared__ AccT front;
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   const AccT ident = OpT::template identity<AccT>();
   AccT p = ident;
   for (unsigned i = threadIdx.x; i < blockIdx.x; i += kScanBlock) p = OpT::apply(p, static_cast<const AccT*>(a.partials)[i]);
@@ -327,6 +329,7 @@ __global__ __launch_bounds__(kScanBlock) void scan_chained(ScanArgs a) {
   __shared__ AccT s_excl;
   __shared__ uint64_t s_tile;
   __shared__ unsigned s_flag;
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   const AccT ident = OpT::template identity<AccT>();
   const unsigned e = __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
   // a sticky error means an earlier launch failed: look once, do not wait

@@ -78,6 +78,7 @@ __global__ __launch_bounds__(kScanBlock) void segment_tiles(SegArgs a) {
   __shared__ AccT s_row[kSegRows];
   __shared__ AccT s_red[kSegWaves];
   __shared__ unsigned s_rowflags;
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   const AccT ident = OpT::template identity<AccT>();
   const T ident_elem = from_acc<T>(ident);
   AccT* const out = static_cast<AccT*>(a.out);
@@ -234,6 +235,7 @@ __global__ __launch_bounds__(kScanBlock) void segment_tiles(SegArgs a) {
 // One wave per tile folds the pieces of the segment that tile owns; then the identities.
 template <class OpT, class AccT>
 __global__ __launch_bounds__(kSpanBlock) void segment_spans(SegArgs a, uint64_t tile_elems) {
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   const AccT ident = OpT::template identity<AccT>();
   AccT* const out = static_cast<AccT*>(a.out);
   const AccT* const first = static_cast<const AccT*>(a.pieces);

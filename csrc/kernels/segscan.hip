@@ -88,6 +88,7 @@ __global__ __launch_bounds__(kScanBlock) void segscan_chunk_totals(SegScanArgs a
   constexpr int N = Vec16<T>::N;
   constexpr uint64_t kTile = kSsTileVecs * N;
   __shared__ AccT lds[kSsWaves];
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   const AccT ident = OpT::template identity<AccT>();
   const T ident_elem = from_acc<T>(ident);
   uint64_t t0, t1;
@@ -264,6 +265,7 @@ __global__ __launch_bounds__(kScanBlock) void segscan_chunks(SegScanArgs a) {
   __shared__ unsigned s_has[kSsRows];
   __shared__ AccT s_front;
   __shared__ unsigned s_start;
+  if constexpr (kFloatMinMax<OpT, AccT>) minmax_ignore_all_nans();
   const AccT ident = OpT::template identity<AccT>();
   const unsigned b = blockIdx.x;
   if (threadIdx.x == 0) s_start = 0;

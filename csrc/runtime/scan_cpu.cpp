@@ -21,7 +21,8 @@ struct Running {
   static constexpr bool kCompensated = std::is_same_v<OpT, SumOp> && std::is_floating_point_v<A>;
   A plain;
   double sum = 0, c = 0;
-  explicit Running(A start) : plain(start), sum(static_cast<double>(start)) {}
+  // (the carry is folded with the identity, not taken as it is: a NaN carry is ignored by MIN / MAX)
+  explicit Running(A start) : plain(OpT::apply(OpT::template identity<A>(), start)), sum(static_cast<double>(start)) {}
   void add(A x) {
     if constexpr (kCompensated) {
       const double d = static_cast<double>(x), t = sum + d;
@@ -33,7 +34,8 @@ struct Running {
     }
   }
   A value() const {
-    if constexpr (kCompensated) return static_cast<A>(sum + c);
+    // (once the sum is infinite or NaN the compensation term is inf - inf = NaN: the sum alone is the answer)
+    if constexpr (kCompensated) return static_cast<A>(std::isfinite(sum) ? sum + c : sum);
     else return plain;
   }
 };

@@ -29,7 +29,8 @@ void segments_typed(const T* in, const int64_t* off, uint64_t S, A* out) {
         else c += (d - t) + sum;
         sum = t;
       }
-      out[s] = static_cast<A>(sum + c);
+      // (once the sum is infinite or NaN the compensation term is inf - inf = NaN: the sum alone is the answer)
+      out[s] = static_cast<A>(std::isfinite(sum) ? sum + c : sum);
     } else {
       A acc = OpT::template identity<A>();
       for (int64_t i = lo; i < hi; ++i) acc = OpT::apply(acc, OpT::pre(static_cast<A>(in[i])));

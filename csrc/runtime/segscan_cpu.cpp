@@ -34,7 +34,8 @@ struct Running {
     }
   }
   A value() const {
-    if constexpr (kCompensated) return static_cast<A>(sum + c);
+    // (once the sum is infinite or NaN the compensation term is inf - inf = NaN: the sum alone is the answer)
+    if constexpr (kCompensated) return static_cast<A>(std::isfinite(sum) ? sum + c : sum);
     else return plain;
   }
 };
